@@ -7,11 +7,16 @@ RCCL all-gather of the (B,T',66) pose parameters to every rank over xGMI
 IK frame := one window -> one solved frame (inference.py:58-64).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--T T]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
-Rank 0 prints ONE JSON line with the metric, the roofline of the dominant
-kernel (HIP events around its launches inside the timed region) and a CPU
-baseline (the oracle, fixture-pinned to the reference, on host cores).
+A plain run sets up, warms up, times the K steps and rank 0 prints ONE JSON
+line with the metric. --dump-outputs DIR also writes what the last timed step
+returned as DIR/<name>.npy. --full adds, to the same line, the roofline of the
+dominant kernel (a second pass of the K steps with HIP events around its
+launches), the other precision, the gather check at N>1, BASELINE configs #4
+and #5 and a CPU baseline (the oracle, fixture-pinned to the reference, on
+host cores).
 """
 from __future__ import annotations
 
@@ -212,6 +217,24 @@ def _cpu_baseline(T: int, seconds: float = 12.0):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
+DUMP_BYTES_MAX = 64 << 20   # --dump-outputs: all files together
+
+
+def _dump_outputs(out_dir, arrays):
+    """Write each (name, array) as out_dir/<name>.npy in float32 / float64. An
+    array over its share of DUMP_BYTES_MAX is cut to a fixed, seeded sample of
+    its rows (leading axis, in ascending order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(1, len(arrays))
+    for name, a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            rows = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -219,6 +242,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1024, help="windows per GPU")
     ap.add_argument("--T", type=int, default=64, help="frames per window")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline pass, the other precision, the gather check (N>1), "
+                         "configs #4/#5 and the CPU baseline (each can be dropped with its --no-* option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--precision", default="bf16x3", choices=["bf16x3", "fp32"],
@@ -286,6 +314,8 @@ def main():
         h = reg.tik_handle()
         per_fwd = 2 * len(reg.backbone.st_gcn_networks) + 4
 
+        last = [None]   # what the latest step returned
+
         def timed(k):
             """k steps between barrier + synchronize on both sides; max over ranks"""
             if world > 1:
@@ -293,7 +323,7 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(k):
-                step()
+                last[0] = step()
             gathers.drain()
             torch.cuda.synchronize()
             if world > 1:
@@ -308,10 +338,16 @@ def main():
         # timed region 1: the metric (no instrumentation: one HIP event pair per
         # launch costs ~3.5 us per event on this path, ~3.5 % of a step)
         dt = timed(args.steps)
+        if args.dump_outputs and rank == 0 and last[0] is not None:
+            # the last timed step's poses (this rank's) and, at N>1, the gathered poses of every rank
+            outs = [("poses", last[0].cpu().numpy())]
+            if world > 1:
+                outs.append(("poses_gathered", full.cpu().numpy()))
+            _dump_outputs(args.dump_outputs, outs)
         # timed region 2: the same K steps with a HIP event pair around every
         # launch on its stream (tik_model_profile): per-kernel durations for the roofline
         dt_prof = None
-        if not args.no_profile:
+        if args.full and not args.no_profile:
             _lib.check(lib.tik_model_profile(h, per_fwd * args.steps))
             dt_prof = timed(args.steps)
 
@@ -333,7 +369,7 @@ def main():
     # N > 1: the gathered poses of the last step are checked on rank 0 against
     # its own solve of every rank's windows (the inputs are seeded per rank)
     gather_check = None
-    if world > 1:
+    if world > 1 and args.full:
         with torch.no_grad():
             step()
             gathers.drain()
@@ -347,7 +383,7 @@ def main():
     ms_step = dt / args.steps * 1e3
     value = world * B / (dt / args.steps)
     others = []
-    if not args.no_compare:
+    if args.full and not args.no_compare:
         # the other arithmetics on the same inputs: time + max |difference| of the poses
         with torch.no_grad():
             y_main = reg(x)["poses"].clone()
@@ -370,7 +406,27 @@ def main():
                                "ms_per_step": round(dt_alt / args.steps * 1e3, 4),
                                "max_abs_pose_diff_vs_main": float((y_main - y_alt).abs().max().item())})
             reg.tik_precision = args.precision
-    if rank == 0 and args.no_profile:
+    if rank == 0 and not args.full:
+        print(json.dumps({
+            "metric": "IK frames/sec (COCO-17->SMPLx pose)",
+            "value": round(value, 1),
+            "unit": "IK frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 4),
+            "pose_rows_per_s": round(value * Tp, 1),   # windows/s x T' output rows
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": DTYPE[args.precision],
+            "data": "synthetic (AMASS-shaped windows from the sample sequence; seeded synthetic weights)",
+            "config": {"workload": f"ST-GCN IK forward, batch={B}x{T}-frame x COCO-17 windows per GPU -> (B,{Tp},66) "
+                                   f"SMPL-X pose" + (f", RCCL all-gather of poses over {world} GPUs" if world > 1 else ""),
+                       "global_batch": world * B, "window_frames": T, "out_frames": Tp,
+                       "parallelism": f"dp{world}" if world > 1 else "single"},
+            "timing": "value/ms_per_step: K steps with no instrumentation"}))
+    elif rank == 0 and args.no_profile:
         print(json.dumps({"metric": "IK frames/sec (COCO-17->SMPLx pose)", "value": round(value, 1),
                           "ms_per_step": round(ms_step, 4), "note": "diagnostic run without per-launch events"}))
     elif rank == 0:

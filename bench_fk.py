@@ -5,7 +5,7 @@
 Prints one JSON line: bodies/s, and per kernel (HIP events around every launch
 of a second pass of the same steps, tik_fk_profile) the algorithmic TFLOP/s of
 the blend-shape and skinning GEMMs against the bf16x3 MFMA roof and the
-vertex bytes over HBM; then the oracle CPU baseline. bench.py reuses
+vertex bytes over HBM; then the oracle CPU baseline. bench.py --full reuses
 measure_fk() for its "fk" key.
 """
 import argparse, ctypes, json, os, sys, time

@@ -3,7 +3,7 @@ step, per-frame latency (push of one frame -> its solved pose on the host).
 
     python bench_stream.py [--frames 10000] [--warmup 100] [--win 64]
 
-bench.py reuses measure_online() for its "online" key.
+bench.py --full reuses measure_online() for its "online" key.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))

@@ -15,10 +15,10 @@ i=0
 for lib in "$OLD" "" "$OLD" ""; do
   i=$((i + 1))
   name=${lib:-new}
-  TIK_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-compare --no-extras --steps 30 > $OUT/ablib_${TAG}_$i.json 2> $OUT/ablib_${TAG}_$i.err || exit $?
+  TIK_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-compare --no-extras --steps 30 > $OUT/ablib_${TAG}_$i.json 2> $OUT/ablib_${TAG}_$i.err || exit $?
   python -c "import json;d=json.load(open('$OUT/ablib_${TAG}_$i.json'));k=d.get('forward',{}).get('kernels') or d.get('kernels',{});print('$name', d['value'], d['ms_per_step'], {n:round(v['avg_ms'],4) for n,v in k.items()})"
 done
-B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-compare --no-extras"
+B="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-compare --no-extras"
 for lib in "$OLD" ""; do
   name=$([ -n "$lib" ] && echo old || echo new)
   TIK_SPLIT=0 TIK_LIB=$lib timeout -s KILL 120 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $OUT/abfetch_${TAG}_$name -o run -- $B > /dev/null 2> $OUT/abfetch_${TAG}_$name.err || exit $?

@@ -15,7 +15,7 @@ if [ "$WHAT" = fk ] || [ "$WHAT" = all ]; then
   cat $OUT/fk_$TAG.json; echo "fk rc=$rc"; [ $rc -eq 0 ] || exit $rc
 fi
 if [ "$WHAT" = ik ] || [ "$WHAT" = all ]; then
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-compare --no-extras > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; rc=$?
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-compare --no-extras > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; rc=$?
   python -c "import json;d=json.load(open('$OUT/bench_$TAG.json'));print(d['value'],d['ms_per_step']);[print(k,v) for k,v in d['forward']['launches'].items()]"; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 fi
 exit 0

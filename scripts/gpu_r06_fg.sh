@@ -13,6 +13,6 @@ i=0
 for cfg in "TIK_XFG=0" "-" "TIK_XFG=0" "-"; do
   i=$((i + 1))
   envs=""; [ "$cfg" = "-" ] || envs="$cfg"
-  env $envs timeout -k 10 300 python bench.py --no-cpu-baseline --no-compare --no-extras --steps 30 > $OUT/ab_${TAG}_$i.json 2> $OUT/ab_${TAG}_$i.err || exit $?
+  env $envs timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-compare --no-extras --steps 30 > $OUT/ab_${TAG}_$i.json 2> $OUT/ab_${TAG}_$i.err || exit $?
   python -c "import json;d=json.load(open('$OUT/ab_${TAG}_$i.json'));k=d.get('forward',{}).get('launches',{});print('$cfg', d['value'], d['ms_per_step'], {n:v['avg_ms'] for n,v in k.items()})"
 done

@@ -8,5 +8,5 @@ for i in 1 2; do
   for v in old new; do echo "== $v"; timeout -k 10 60 ./build/xwbench_$v 1024 32 20 || exit 1; done
 done > $O/xwbench_r06h.txt 2>&1
 cat $O/xwbench_r06h.txt
-timeout -k 10 120 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-compare --no-extras > $O/bench_r06h.json 2> $O/bench_r06h.err || exit 1
+timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-compare --no-extras > $O/bench_r06h.json 2> $O/bench_r06h.err || exit 1
 python -c "import json;d=json.load(open('$O/bench_r06h.json'));print(d['ms_per_step'], d['forward']['launches'].get('XTWG.L3'), d['forward']['launches'].get('XTWG.L4'))"

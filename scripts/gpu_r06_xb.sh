@@ -6,7 +6,7 @@ timeout -k 10 200 python -u -m pytest -x -v --timeout 120 --timeout-method threa
 tail -2 $O/pytest_r06xb.log
 for i in 1 2; do
   for v in 00 10 01 11; do
-    TIK_LIB=$GRAFT_REPO_ROOT/build/ab/libtik_xb$v.so timeout -k 10 120 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-compare --no-extras > $O/bench_r06xb_$v.json 2> $O/bench_r06xb_$v.err || exit 1
+    TIK_LIB=$PWD/build/ab/libtik_xb$v.so timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-compare --no-extras > $O/bench_r06xb_$v.json 2> $O/bench_r06xb_$v.err || exit 1
     python -c "
 import json;d=json.load(open('$O/bench_r06xb_$v.json'));L=d['forward']['launches']
 print('$v', d['ms_per_step'], 'XB0 %.4f XB1 %.4f' % (L['XB0.L0']['avg_ms'], L['XB1.L1']['avg_ms']))"

@@ -6,7 +6,7 @@ TIK_LIB=$GRAFT_REPO_ROOT/build/ab/libtik_xgs.so timeout -k 10 200 python -u -m p
 tail -1 $O/pytest_r06xgs.log
 for i in 1 2 3; do
   for v in base xgs; do
-    TIK_LIB=$GRAFT_REPO_ROOT/build/ab/libtik_$v.so timeout -k 10 120 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-compare --no-extras > $O/bench_r06xgs.json 2> $O/bench_r06xgs.err || exit 1
+    TIK_LIB=$PWD/build/ab/libtik_$v.so timeout -k 10 120 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-compare --no-extras > $O/bench_r06xgs.json 2> $O/bench_r06xgs.err || exit 1
     python -c "
 import json;d=json.load(open('$O/bench_r06xgs.json'));L=d['forward']['launches']
 print('%-5s' % '$v', d['ms_per_step'], ' '.join('%s %.4f' % (k, v['avg_ms']) for k, v in L.items() if k.startswith(('XGW','XT128.L2'))))"

@@ -24,7 +24,7 @@ echo "== pmc passes + kernel stats (single-stream)"
 bash scripts/gpu_pmc_all.sh $TAG; rc=$?
 echo "pmc rc=$rc"; [ $rc -eq 0 ] || exit $rc
 echo "== bench"
-timeout -k 10 400 python bench.py --pmc-traffic $OUT/pmc_traffic_$TAG.json --pmc-mfma $OUT/pmc_mfma_$TAG.json > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; rc=$?
+timeout -k 10 400 python bench.py --full --pmc-traffic $OUT/pmc_traffic_$TAG.json --pmc-mfma $OUT/pmc_mfma_$TAG.json > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; rc=$?
 tail -c 1500 $OUT/bench_$TAG.json; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 echo "== stream"
 timeout -k 10 300 python bench_stream.py --frames 3000 > $OUT/stream_$TAG.json 2> $OUT/stream_$TAG.err; rc=$?

@@ -38,7 +38,7 @@ def main():
         res[k] = {"dispatches": len(busy), "mfma_busy_cycles_per_dispatch": b, "gui_active_per_dispatch": g,
                   "kernel_cycles": cyc, "mfma_busy_frac": b / (cyc * nsimd) if cyc > 0 else None}
     json.dump({"source_digest": source_digest(), "method": "rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE on "
-                         "'bench.py --steps 3 --warmup 1'; busy / (GRBM_GUI_ACTIVE / 8 x %d SIMDs)" % nsimd,
+                         "'bench.py --full --steps 3 --warmup 1'; busy / (GRBM_GUI_ACTIVE / 8 x %d SIMDs)" % nsimd,
                "kernels": res}, open(out, "w"), indent=1)
     for k, v in res.items():
         print(f"{k[:70]:<70} n={v['dispatches']:4d} busy={v['mfma_busy_cycles_per_dispatch']:.3e} "

@@ -39,7 +39,7 @@ def main():
         res[k] = {"dispatches": len(fetch.get(k, [])), "fetch_bytes_per_dispatch": fb,
                   "write_bytes_per_dispatch": wb, "hbm_bytes_per_dispatch": fb + wb}
     json.dump({"source_digest": source_digest(), "method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) on "
-                         "'bench.py --steps 3 --warmup 1'; FETCH_SIZE KB x 1024 x 2 (gfx950 half-count), "
+                         "'bench.py --full --steps 3 --warmup 1'; FETCH_SIZE KB x 1024 x 2 (gfx950 half-count), "
                          "WRITE_SIZE KB x 1024; averaged over the kernel's dispatches",
                "kernels": res}, open(out, "w"), indent=1)
     for k, v in res.items():

@@ -166,3 +166,22 @@ def test_bench_kernel_symbols_resolve():
     for label in ("XT128", "XH128", "XR", "XGW", "XTWG", "XB0", "XB1", "XG128", "XP64", "G0f_raw"):
         sym = bench.kernel_symbol(label, "bf16x3")
         assert sym and any(n == sym or ("<" not in sym and n.startswith(sym + "<")) for n in names), (label, sym)
+
+
+def test_bench_dump_outputs_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 .npy files, together within
+    DUMP_BYTES_MAX; a larger array is cut to the same seeded rows every time."""
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4096)
+    rng = np.random.default_rng(1)
+    small = rng.standard_normal((5, 3)).astype(np.float16)
+    big = rng.standard_normal((100, 4, 8))   # 25,600 B of float64 against a 2048 B share
+    for d in ("a", "b"):
+        bench._dump_outputs(str(tmp_path / d), [("small", small), ("big", big)])
+    sa, ba = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert sa.dtype == np.float32 and ba.dtype == np.float64
+    np.testing.assert_array_equal(sa, small.astype(np.float32))
+    assert sa.nbytes + ba.nbytes <= 4096 and ba.shape == (8, 4, 8)
+    rows = [int(np.flatnonzero((big == r).all(axis=(1, 2)))[0]) for r in ba]
+    assert rows == sorted(set(rows))
+    np.testing.assert_array_equal(ba, np.load(tmp_path / "b" / "big.npy"))
