@@ -42,6 +42,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--eval", action="store_true",
+                    help="also time GpuTrainer.validation_step on the same batches, in this process")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -82,6 +84,20 @@ def main():
                         "frac": round(fl * B / dt / 1e12 / 157.3, 4),
                         "peak_basis": "dense fp32 MFMA (v_mfma_f32_16x16x4_f32), MI355X_MICROARCH.md"},
            "loss_last": float(loss)}
+    if a.eval:
+        # the eval-mode pass on the live weights (tik_trainer_eval), same batches, same process
+        batches = [{"keypoints_3d": xs[i], "poses": ys[i]} for i in range(4)]
+        for i in range(max(a.warmup, 1)):
+            tr.validation_step(batches[i % 4], i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(a.steps):
+            vl = tr.validation_step(batches[i % 4], i)["val_loss"]
+        torch.cuda.synchronize()
+        de = (time.perf_counter() - t0) / a.steps
+        out["eval"] = {"metric": "validation_step (eval-mode forward + MSE on the trainer's live weights)",
+                       "ms_per_batch": round(de * 1e3, 4), "value": round(B / de, 1), "unit": "windows/s",
+                       "train_step_ms": round(dt * 1e3, 4), "val_loss_last": float(vl)}
     if not a.no_cpu_baseline:
         from oracle import train as otr
         nb = 16

@@ -239,6 +239,26 @@ int tik_trainer_count(tik_trainer_t t);
 int tik_trainer_tensor(tik_trainer_t t, int i, char* name, int name_len, int64_t* shape4, int* ndim, int* kind);
 int tik_trainer_read(tik_trainer_t t, int i, int what, float* dst, void* stream);
 long long tik_trainer_steps(tik_trainer_t t);
+/* Validation and resume.
+ * tik_trainer_eval: eval-mode forward on the trainer's current weights
+ *   (BatchNorm on the running statistics, folded into the fp32 GEMM operands
+ *   on the device; no dropout). poses (N,T',pose_dim) and loss (device scalar,
+ *   mean((poses - target)^2)) are each optional; target is required iff
+ *   loss != NULL. Changes no trainer state (parameters, gradients, Adam
+ *   moments, running statistics, saved activations, steps). N*T == 1 is
+ *   allowed (no batch statistics are taken), and a window's poses do not
+ *   depend on the rest of the batch. Stream-ordered.
+ * tik_trainer_write: the inverse of tik_trainer_read: device src -> value /
+ *   gradient / exp_avg / exp_avg_sq of tensor i (buffers: what == 0 only).
+ *   The derived GEMM layouts and the eval set are refreshed before their next
+ *   use.
+ * tik_trainer_set_steps: the update count (>= 0) that tik_trainer_steps
+ *   reports and Adam's bias correction continues from (resuming a
+ *   checkpoint; GpuTrainer also keys its dropout seed on it). */
+int tik_trainer_eval(tik_trainer_t t, const float* x, int N, int T, const float* target, float* poses, float* loss,
+                     void* stream);
+int tik_trainer_write(tik_trainer_t t, int i, int what, const float* src, void* stream);
+int tik_trainer_set_steps(tik_trainer_t t, long long steps);
 /* Debug / test hook: the last step's saved activations of block `layer`
  * (which 0 output, 2 tcn conv output, 3 post-ReLU tcn input, 4 graph-mix
  * output, 5 gcn conv output; 6 the head's first Linear output), and with

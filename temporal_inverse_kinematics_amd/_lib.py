@@ -85,6 +85,9 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_trainer_read": (_I, (_P, _I, _I, _P, _P)),
     "tik_trainer_steps": (ctypes.c_longlong, (_P,)),
     "tik_trainer_debug": (_I, (_P, _I, _I, _P, ctypes.c_longlong, _P)),
+    "tik_trainer_eval": (_I, (_P, _P, _I, _I, _P, _P, _P, _P)),
+    "tik_trainer_write": (_I, (_P, _I, _I, _P, _P)),
+    "tik_trainer_set_steps": (_I, (_P, ctypes.c_longlong)),
 }
 
 _lib = None

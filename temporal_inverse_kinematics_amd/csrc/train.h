@@ -88,6 +88,36 @@ hipError_t launch_leaky_dropout_bwd(float* dP, const float* dD, const float* P, 
 // cols floats, dO rows of ldo (padding columns zeroed)
 hipError_t launch_mse(const float* O, int ldo, const float* T, long long rows, int cols, float* dO, float* loss,
                       hipStream_t st);
+// Eval-mode BatchNorm folded into the forward GEMM operands (the host fold of
+// api.cpp's Layer::build, on the device, from the live parameters): per
+// channel sc = gamma / sqrt(running_var + eps) (the root in double), sh =
+// beta - running_mean * sc. One descriptor per output tensor dst[rows][cols]:
+//   FOLD_SCALE  dst[co][k] = sc[co] * src[co][k]                       (conv weights, channel = row)
+//   FOLD_BIAS2  dst[w][co] = sc[co] * src[co] * sum_v aux[v][w] + sh[co]   (src: gcn bias, aux: A_eff [V][V], rows = V)
+//   FOLD_BIAST  dst[co] = sc[co] * src[co] + sh[co] (+ sc2[co] * aux[co] + sh2[co], aux: residual conv bias)
+//   FOLD_DATA   dst[0][c] = sc[cmap[c]], dst[1][c] = sh[cmap[c]] (0 where cmap[c] < 0), rows = 2
+struct BnRef {
+    const float *gamma, *beta, *mean, *var;
+};
+enum { FOLD_SCALE = 0, FOLD_BIAS2 = 1, FOLD_BIAST = 2, FOLD_DATA = 3 };
+struct FoldDesc {
+    int kind, rows, cols;
+    float* dst;
+    const float* src;
+    const float* aux;
+    BnRef bn, bn2;
+    const int* cmap;
+    long long block0;   // first workgroup (fold_batch_blocks)
+};
+// assigns block ranges; returns the grid size
+long long fold_batch_blocks(FoldDesc* descs, int nd);
+hipError_t launch_fold_batch(const FoldDesc* descs_dev, int nd, long long blocks, float eps, hipStream_t st);
+// loss[0] = mean((O - T)^2), no gradient: O rows of ldo, T rows of cols floats. Workgroups
+// write double partial sums to part (>= mse_eval_blocks(rows * cols) doubles), one
+// workgroup adds them in a fixed order.
+int mse_eval_blocks(long long n);
+hipError_t launch_mse_eval(const float* O, int ldo, const float* T, long long rows, int cols, float* loss, double* part,
+                           hipStream_t st);
 // torch.optim.Adam (single-tensor path): m = lerp(m, g, 1-b1); v = v*b2 + (1-b2) g^2;
 // p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2,

@@ -738,6 +738,126 @@ hipError_t launch_mse(const float* O, int ldo, const float* T, long long rows, i
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- eval pass
+// eval-mode BatchNorm of channel c as (scale, shift), the arithmetic of the
+// host fold (api.cpp bn_fold): the scale in double, both rounded to fp32 once
+__device__ __forceinline__ void bn_eval_affine(const BnRef& b, int c, float eps, float& sc, float& sh) {
+    const double s = (double)b.gamma[c] / sqrt((double)b.var[c] + (double)eps);
+    sc = (float)s;
+    sh = (float)((double)b.beta[c] - (double)b.mean[c] * s);
+}
+
+// the eval set of every layer in one launch: workgroup b serves the descriptor
+// whose block range holds b, 1024 outputs per workgroup (as permute_batch_kernel).
+// Deliberately plain: the linear scan of the ~40 descriptors and the per-thread
+// 17-term column sum of FOLD_BIAS2 run once per weight version, not per batch.
+__global__ __launch_bounds__(256) void fold_batch_kernel(const FoldDesc* __restrict__ descs, int nd, float eps) {
+    int d = 0;
+    while (d + 1 < nd && descs[d + 1].block0 <= (long long)blockIdx.x) ++d;
+    const FoldDesc& q = descs[d];
+    const long long n = (long long)q.rows * q.cols;
+    for (long long i = (blockIdx.x - q.block0) * 1024LL + threadIdx.x, e = 0; e < 4; ++e, i += 256) {
+        if (i >= n) return;
+        const int r = (int)(i / q.cols), c = (int)(i % q.cols);
+        float sc, sh;
+        if (q.kind == FOLD_SCALE) {
+            bn_eval_affine(q.bn, r, eps, sc, sh);
+            q.dst[i] = sc * q.src[i];
+        } else if (q.kind == FOLD_BIAS2) {
+            bn_eval_affine(q.bn, c, eps, sc, sh);
+            double colsum = 0.0;
+            for (int v = 0; v < q.rows; ++v) colsum += (double)q.aux[v * q.rows + r];
+            q.dst[i] = (float)((double)sc * (double)q.src[c] * colsum + (double)sh);
+        } else if (q.kind == FOLD_BIAST) {
+            bn_eval_affine(q.bn, c, eps, sc, sh);
+            float b = (float)((double)sc * (double)q.src[c] + (double)sh);
+            if (q.aux) {
+                bn_eval_affine(q.bn2, c, eps, sc, sh);
+                b += (float)((double)sc * (double)q.aux[c] + (double)sh);
+            }
+            q.dst[i] = b;
+        } else {   // FOLD_DATA
+            const int ch = q.cmap[c];
+            sc = sh = 0.f;
+            if (ch >= 0) bn_eval_affine(q.bn, ch, eps, sc, sh);
+            q.dst[i] = r == 0 ? sc : sh;
+        }
+    }
+}
+
+long long fold_batch_blocks(FoldDesc* descs, int nd) {
+    long long b = 0;
+    for (int d = 0; d < nd; ++d) {
+        descs[d].block0 = b;
+        b += ((long long)descs[d].rows * descs[d].cols + 1023) / 1024;
+    }
+    return b;
+}
+
+hipError_t launch_fold_batch(const FoldDesc* descs_dev, int nd, long long blocks, float eps, hipStream_t st) {
+    if (nd == 0 || blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(fold_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, st, descs_dev, nd, eps);
+    return hipGetLastError();
+}
+
+// validation loss: workgroup b sums its contiguous chunk of (O - T)^2 in double
+// (threads strided inside the chunk, LDS tree), part[b]; the finalize workgroup
+// adds the partials in a fixed order. No gradient, no atomics.
+constexpr int MSE_CHUNK = 4096;    // elements per workgroup pass
+constexpr int MSE_MAX_BLOCKS = 1024;
+
+__device__ __forceinline__ double block_sum_256(double s, double* red) {
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(256) void mse_eval_kernel(const float* __restrict__ O, int ldo, const float* __restrict__ T,
+                                                       long long n, int cols, long long per_block,
+                                                       double* __restrict__ part) {
+    __shared__ double red[256];
+    const long long lo = (long long)blockIdx.x * per_block;
+    const long long hi = lo + per_block < n ? lo + per_block : n;
+    double s = 0.0;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+        const long long r = i / cols;
+        const int c = (int)(i - r * cols);
+        const float d = O[r * ldo + c] - T[i];
+        s += (double)d * d;
+    }
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void mse_eval_finalize_kernel(const double* __restrict__ part, int nb, long long n,
+                                                                float* __restrict__ loss) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) s += part[i];
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) loss[0] = (float)(s / (double)n);
+}
+
+int mse_eval_blocks(long long n) {
+    const long long b = (n + MSE_CHUNK - 1) / MSE_CHUNK;
+    return (int)(b < 1 ? 1 : (b > MSE_MAX_BLOCKS ? MSE_MAX_BLOCKS : b));
+}
+
+hipError_t launch_mse_eval(const float* O, int ldo, const float* T, long long rows, int cols, float* loss, double* part,
+                           hipStream_t st) {
+    const long long n = rows * cols;
+    if (n <= 0 || cols > ldo) return hipErrorInvalidValue;
+    const int nb = mse_eval_blocks(n);
+    const long long per_block = (n + nb - 1) / nb;
+    hipLaunchKernelGGL(mse_eval_kernel, dim3(nb), dim3(256), 0, st, O, ldo, T, n, cols, per_block, part);
+    hipLaunchKernelGGL(mse_eval_finalize_kernel, dim3(1), dim3(256), 0, st, part, nb, n, loss);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- Adam
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long long n, float w1, float b2, float w2, float step_size,

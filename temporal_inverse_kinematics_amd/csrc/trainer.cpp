@@ -54,6 +54,7 @@ struct TLayer {
               b3 = -1, E = -1;
     long long rm1 = -1, rv1 = -1, rm2 = -1, rv2 = -1, rm3 = -1, rv3 = -1;
     DevBuf wgf, wgb, wtf, wtb, wrf, wrb, aeff;     // derived GEMM layouts
+    DevBuf wg_e, b2_e, wt_e, bT_e, wr_e;            // eval set: eval-mode BatchNorm folded into wgf / wtf / wrf and the biases
     DevBuf Y, Z, H, U, Q, O;                        // saved activations
     DevBuf st1, st2, st3;                           // [4][C] mean, invstd, scale, shift
     int tin = 0, tout = 0;
@@ -92,6 +93,19 @@ struct tik_trainer {
     std::vector<DevBuf> dbg_dx;   // TIK_TRAIN_DEBUG=1: each block's input gradient of the last step
     DevBuf dbg_b[5];              // TIK_TRAIN_DEBUG_LAYER=l: that block's gS, dU, dH (post-ReLU), dZ, dY
     float lr = 1e-4f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, momentum = 0.1f;
+    // eval pass (tik_trainer_eval): the folded eval set is valid for weight version
+    // `folded_at`; step() and tik_trainer_write bump `version`
+    long long version = 1, folded_at = 0;
+    bool derive_stale = false;        // a written value: the derived GEMM layouts follow before the next use
+    bool mix_sparse = false;          // A (hence A_eff) lies inside the COCO hop<=2 pattern
+    DevBuf dbn_e;                     // [2][4*V] folded data_bn scale, shift on the padded columns
+    DevArray<unsigned char> fold;     // eval-set descriptors (tik::FoldDesc)
+    int nfold = 0;
+    long long fold_blocks = 0;
+    struct {                          // the eval pass's own workspace, grown on demand
+        DevBuf x4, x0, z, a0, a1, ph, oh;
+        DevArray<double> part;
+    } ev;
 };
 
 namespace {
@@ -391,6 +405,11 @@ int step(tik_trainer* t, const float* x, int N, int T, const float* target, cons
         HIP_TRY(hipMemsetAsync(t->gB.p, 0, t->gB.n * sizeof(float), st));
         t->zero_pending = false;
     }
+    if (t->derive_stale) {   // a value written since the last step (tik_trainer_write)
+        if ((rc = derive(t, st))) return rc;
+        t->derive_stale = false;
+    }
+    t->version += 1;         // this step changes the weights and running statistics: the eval set refolds
     (void)hipGetLastError();
     const long long R0 = (long long)N * T, p0 = R0 * V;
     float* P = t->P.p;
@@ -480,6 +499,129 @@ int step(tik_trainer* t, const float* x, int N, int T, const float* target, cons
     const double bc2 = 1.0 - std::pow((double)t->beta2, (double)t->steps);
     HIP_TRY(tik::launch_adam(P, Gd, t->M.p, t->Vv.p, t->np, t->lr, t->beta1, t->beta2, t->eps, bc1, bc2, st));
     return derive(t, st);
+}
+
+// ---------------------------------------------------------------- eval pass
+// The eval set from the live parameters, running statistics and derived
+// layouts: one batched launch over a descriptor table built once.
+int fold(tik_trainer* t, hipStream_t st) {
+    if (!t->fold.p) {
+        const float* P = t->P.p;
+        const float* B = t->B.p;
+        std::vector<tik::FoldDesc> d;
+        auto bn = [&](long long g, long long b, long long rm, long long rv) {
+            return tik::BnRef{P + g, P + b, B + rm, B + rv};
+        };
+        auto add = [&](int kind, int rows, int cols, float* dst, const float* src, const float* aux, tik::BnRef b1,
+                       tik::BnRef b2, const int* cmap) {
+            tik::FoldDesc q{kind, rows, cols, dst, src, aux, b1, b2, cmap, 0};
+            d.push_back(q);
+        };
+        const tik::BnRef none{nullptr, nullptr, nullptr, nullptr};
+        add(tik::FOLD_DATA, 2, 4 * V, t->dbn_e.p, nullptr, nullptr, bn(t->dg, t->db, t->rm0, t->rv0), none, t->cmap0.p);
+        for (TLayer& l : t->L) {
+            const int co = l.cout;
+            const tik::BnRef b1 = bn(l.g1, l.b1, l.rm1, l.rv1), b2 = bn(l.g2, l.b2, l.rm2, l.rv2);
+            const bool rc_ = l.res == RES_C;
+            const tik::BnRef b3 = rc_ ? bn(l.g3, l.b3, l.rm3, l.rv3) : none;
+            add(tik::FOLD_SCALE, co, l.cinp, l.wg_e.p, l.wgf.p, nullptr, b1, none, nullptr);
+            add(tik::FOLD_BIAS2, V, co, l.b2_e.p, P + l.bg, l.aeff.p, b1, none, nullptr);
+            add(tik::FOLD_SCALE, co, 3 * co, l.wt_e.p, l.wtf.p, nullptr, b2, none, nullptr);
+            add(tik::FOLD_BIAST, 1, co, l.bT_e.p, P + l.bt, rc_ ? P + l.br : nullptr, b2, b3, nullptr);
+            if (rc_) add(tik::FOLD_SCALE, co, l.cinp, l.wr_e.p, l.wrf.p, nullptr, b3, none, nullptr);
+        }
+        t->fold_blocks = tik::fold_batch_blocks(d.data(), (int)d.size());
+        t->nfold = (int)d.size();
+        std::vector<unsigned char> bytes(d.size() * sizeof(tik::FoldDesc));
+        memcpy(bytes.data(), d.data(), bytes.size());
+        int rc;
+        if ((rc = t->fold.upload(bytes))) return rc;
+    }
+    HIP_TRY(tik::launch_fold_batch(reinterpret_cast<const tik::FoldDesc*>(t->fold.p), t->nfold, t->fold_blocks, BN_EPS,
+                                   st));
+    return TIK_OK;
+}
+
+// Eval-mode forward on the live weights: pad, folded data_bn, two GEMM launches
+// per block (gcn + graph mix + ReLU; temporal conv + residual + ReLU), the head
+// without dropout. No split-K anywhere: a window's poses do not depend on
+// what else is in the batch. Reads P / B / the derived layouts; writes only
+// the eval set and the eval workspace.
+int eval(tik_trainer* t, const float* x, int N, int T, const float* target, float* poses, float* loss, hipStream_t st) {
+    int rc;
+    if (t->derive_stale) {
+        if ((rc = derive(t, st))) return rc;
+        t->derive_stale = false;
+    }
+    // workspace: z (a block's graph-mix output), the activation ping-pong, the head
+    long long zsz = 0, asz = 0;
+    int tin = T;
+    for (const TLayer& l : t->L) {
+        const int to = (tin - 1) / l.stride + 1;
+        zsz = std::max(zsz, (long long)N * tin * V * l.cout);
+        asz = std::max(asz, (long long)N * to * V * l.cout);
+        tin = to;
+    }
+    const int Tp = tin;
+    const long long rows = (long long)N * Tp, p0 = (long long)N * T * V;
+    if ((rc = t->ev.x4.reserve(p0 * 4)) || (rc = t->ev.x0.reserve(p0 * 4)) || (rc = t->ev.z.reserve(zsz)) ||
+        (rc = t->ev.a0.reserve(asz)) || (rc = t->ev.a1.reserve(asz)) || (rc = t->ev.ph.reserve(rows * HIDDEN)) ||
+        (rc = t->ev.oh.reserve(rows * t->pose_dim)) ||
+        (rc = t->ev.part.reserve((size_t)tik::mse_eval_blocks(rows * t->pose_dim))))
+        return rc;
+    (void)hipGetLastError();
+    if (t->folded_at != t->version) {
+        if ((rc = fold(t, st))) return rc;
+        t->folded_at = t->version;
+    }
+    HIP_TRY(tik::launch_pad_channels(x, p0, 3, 4, t->ev.x4.p, st));
+    HIP_TRY(tik::launch_affine(t->ev.x0.p, t->ev.x4.p, t->dbn_e.p, t->dbn_e.p + 4 * V, nullptr, nullptr, nullptr,
+                               (long long)N * T, 4 * V, 0, st));
+    const float* X = t->ev.x0.p;
+    int ldx = 4;
+    float* bufs[2] = {t->ev.a0.p, t->ev.a1.p};
+    int which = 0;
+    tin = T;
+    for (const TLayer& l : t->L) {
+        const int co = l.cout, to = (tin - 1) / l.stride + 1;
+        tik::CgemmArgs g{};
+        g.M = N * tin * V; g.Nc = co; g.V = V; g.tout = tin;
+        g.seg[0] = seg32(X, l.wg_e.p, l.cinp, ldx, 1, 1, 0, tin, l.cinp);
+        g.nseg = 1; g.bias = l.b2_e.p; g.out = t->ev.z.p; g.ldo = co; g.amix = l.aeff.p; g.act = tik::ACT_RELU;
+        g.mix_sparse = t->mix_sparse ? 1 : 0;
+        HIP_TRY(tik::launch_cgemm(g, tik::CFG_G272x64, st, tik::PREC_F32));
+        tik::CgemmArgs u{};
+        u.M = N * to * V; u.Nc = co; u.V = V; u.tout = to;
+        u.seg[0] = seg32(t->ev.z.p, l.wt_e.p, co, co, 3, l.stride, 1, tin, 3 * co);
+        u.nseg = 1;
+        if (l.res == RES_C) {
+            u.seg[1] = seg32(X, l.wr_e.p, l.cinp, ldx, 1, l.stride, 0, tin, l.cinp);
+            u.nseg = 2;
+        } else {
+            u.resid = X; u.ldr = ldx;
+        }
+        u.bias = l.bT_e.p; u.out = bufs[which]; u.ldo = co; u.act = tik::ACT_RELU;
+        HIP_TRY(tik::launch_cgemm(u, co >= 128 ? tik::CFG_T128x128 : tik::CFG_T256x64, st, tik::PREC_F32));
+        X = bufs[which];
+        ldx = co;
+        which ^= 1;
+        tin = to;
+    }
+    // head: Linear + LeakyReLU (Dropout is the identity), Linear (pose_trainer.py:89-92)
+    const float* P = t->P.p;
+    tik::CgemmArgs h{};
+    h.M = (int)rows; h.Nc = HIDDEN; h.V = 1; h.tout = (int)rows;
+    h.seg[0] = seg32(X, P + t->w1, t->feat, t->feat, 1, 1, 0, (int)rows, t->feat);
+    h.nseg = 1; h.bias = P + t->b1; h.out = t->ev.ph.p; h.ldo = HIDDEN; h.act = tik::ACT_LEAKY;
+    HIP_TRY(tik::launch_cgemm(h, tik::CFG_H64x64, st, tik::PREC_F32));
+    float* O = poses ? poses : t->ev.oh.p;
+    tik::CgemmArgs o{};
+    o.M = (int)rows; o.Nc = t->pose_dim; o.V = 1; o.tout = (int)rows;
+    o.seg[0] = seg32(t->ev.ph.p, P + t->w2, HIDDEN, HIDDEN, 1, 1, 0, (int)rows, HIDDEN);
+    o.nseg = 1; o.bias = P + t->b2; o.out = O; o.ldo = t->pose_dim; o.act = tik::ACT_NONE;
+    HIP_TRY(tik::launch_cgemm(o, tik::CFG_H64x64, st, tik::PREC_F32));
+    if (loss) HIP_TRY(tik::launch_mse_eval(O, t->pose_dim, target, rows, t->pose_dim, loss, t->ev.part.p, st));
+    return TIK_OK;
 }
 
 }  // namespace
@@ -587,7 +729,13 @@ int tik_trainer_create(const tik_tensor* tensors, int n_tensors, float lr, tik_t
             (rc = l.st3.reserve(4 * l.cout)))
             return fin(rc);
         if (l.res == RES_C && ((rc = l.wrf.upload(zf)) || (rc = l.wrb.reserve((size_t)l.cin * l.cout)))) return fin(rc);
+        if ((rc = l.wg_e.reserve((size_t)l.cout * l.cinp)) || (rc = l.b2_e.reserve((size_t)V * l.cout)) ||
+            (rc = l.wt_e.reserve(3ULL * l.cout * l.cout)) || (rc = l.bT_e.reserve(l.cout)) ||
+            (l.res == RES_C && (rc = l.wr_e.reserve((size_t)l.cout * l.cinp))))
+            return fin(rc);
     }
+    if ((rc = t->dbn_e.reserve(2 * 4 * V))) return fin(rc);
+    t->mix_sparse = tik::fits_coco_hop2(find(m, bb + "A")->v.data(), V);
     std::vector<float> zw2((size_t)HIDDEN * t->ldp, 0.f);
     if ((rc = t->w1b.reserve((size_t)t->feat * HIDDEN)) || (rc = t->w2b.upload(zw2)) || (rc = t->st0.reserve(4 * 4 * V)) ||
         (rc = t->k.reserve(3 * kmax)) || (rc = t->loss.reserve(1)))
@@ -619,6 +767,41 @@ int tik_trainer_step(tik_trainer_t t, const float* x, int N, int T, const float*
     hipStream_t st = (hipStream_t)stream;
     int rc = step(t, x, N, T, target, dropout_mask, seed, loss ? loss : t->loss.p, st);
     return rc;
+}
+
+int tik_trainer_eval(tik_trainer_t t, const float* x, int N, int T, const float* target, float* poses, float* loss,
+                     void* stream) {
+    if (!t || !x || N <= 0 || T <= 0 || (loss && !target))
+        return fail(TIK_E_INVALID, "tik_trainer_eval: bad arguments (null handle or input, or a loss without a target)");
+    int maxc = 4;
+    for (const TLayer& l : t->L) maxc = std::max(maxc, std::max(l.cinp, l.cout));
+    if ((long long)N * T * V * maxc / 4 > (1LL << 31) - 1 || (long long)N * T * V * 4 > (1LL << 31) - 1)
+        return fail(TIK_E_INVALID, "tik_trainer_eval: batch of %d x %d frames too large", N, T);
+    return eval(t, x, N, T, target, poses, loss, (hipStream_t)stream);
+}
+
+int tik_trainer_write(tik_trainer_t t, int i, int what, const float* src, void* stream) {
+    if (!t || i < 0 || i >= (int)t->ents.size() || !src || what < 0 || what > 3)
+        return fail(TIK_E_INVALID, "tik_trainer_write: bad arguments");
+    const TEntry& e = t->ents[i];
+    if (e.kind == 1 && what != 0)
+        return fail(TIK_E_INVALID, "tik_trainer_write: '%s' is a buffer (it has a value only)", e.name.c_str());
+    float* base = e.kind == 1 ? t->B.p : (what == 0 ? t->P.p : what == 1 ? t->G.p : what == 2 ? t->M.p : t->Vv.p);
+    HIP_TRY(hipMemcpyAsync(base + e.off, src, e.numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (what == 0) {   // the derived GEMM layouts and the eval set follow before their next use
+        t->derive_stale = true;
+        t->version += 1;
+        // a new adjacency may leave the COCO hop<=2 pattern: the dense graph mix is right for any A
+        if (e.kind == 1 && e.off == t->A) t->mix_sparse = false;
+    }
+    return TIK_OK;
+}
+
+int tik_trainer_set_steps(tik_trainer_t t, long long steps) {
+    if (!t) return fail(TIK_E_INVALID, "tik_trainer_set_steps: null handle");
+    if (steps < 0) return fail(TIK_E_INVALID, "tik_trainer_set_steps: steps must be >= 0 (got %lld)", steps);
+    t->steps = steps;
+    return TIK_OK;
 }
 
 int tik_trainer_out_frames(tik_trainer_t t, int T) {

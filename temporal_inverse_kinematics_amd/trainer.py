@@ -15,11 +15,26 @@ Parameters, gradients, Adam state and BatchNorm buffers stay on the device
 between steps; `state_dict()` / `load_into(module)` export them under the
 reference's names (the weight ABI of SURVEY.md §8b), so a trained model
 drops straight into `PoseRegressor` inference or a `.ckpt`.
+
+Around the step: `predict` / `validation_step` run the eval-mode forward on
+the live device weights (`tik_trainer_eval`: running statistics folded on the
+device, no dropout, the fp32 arithmetic being trained; :158-172),
+`save_checkpoint` / `from_checkpoint` write and resume Lightning-shaped
+`.ckpt` files with the Adam state, `fit` is the epoch loop with top-k
+checkpoints and `on_epoch_end` (:174-177, :240-256), and `run_train`
+(`python -m temporal_inverse_kinematics_amd.trainer`) is the reference's
+command line.
 """
 from __future__ import annotations
 
+import argparse
 import ctypes
-from typing import Dict, Optional
+import json
+import os
+import re
+import sys
+from pathlib import Path
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -28,6 +43,7 @@ from . import _lib
 from .models import IKPoseTrainer, PoseRegressor, _Handle, _state_numpy
 
 _WHAT = {"value": 0, "grad": 1, "exp_avg": 2, "exp_avg_sq": 3}
+_CKPT_NAME = re.compile(r"^checkpoint_epoch=(\d+)-val_loss=(-?\d+\.\d\d|nan|inf)\.ckpt$")
 
 
 class GpuTrainer:
@@ -46,6 +62,7 @@ class GpuTrainer:
         if lr is None:
             lr = float(getattr(hp, "lr", 1e-4)) if hp is not None else 1e-4
         self.lr = float(lr)
+        self.hparams = hp
         self.device = torch.device(device)
         self.regressor = reg
         named = _state_numpy(reg)
@@ -146,3 +163,275 @@ class GpuTrainer:
         sd = {k: v.to(own[k].device, own[k].dtype) for k, v in self.state_dict().items() if k in own}
         reg.load_state_dict(sd, strict=False)
         return reg
+
+    def write_tensor(self, name: str, src: torch.Tensor, what: str = "value") -> None:
+        """The inverse of `tensor`: a device tensor -> the value / grad / exp_avg /
+        exp_avg_sq of `name` (tik_trainer_write). Buffers have a value only."""
+        i = self._index[name]
+        _, shape, _ = self._names[i]
+        src = src.contiguous()
+        _lib.require_gpu(src)    # on the device (RuntimeError), float32 (TypeError)
+        if tuple(src.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(src.shape)}")
+        _lib.check(_lib.load().tik_trainer_write(self._h.h, i, _WHAT[what], src.data_ptr(), _lib.stream_of(src)), name)
+
+    # ------------------------------------------------------------------ eval
+    def evaluate(self, keypoints_3d: torch.Tensor, poses: Optional[torch.Tensor] = None, want_poses: bool = True):
+        """Eval-mode forward on the live weights (tik_trainer_eval): BatchNorm on the
+        running statistics, no dropout, the trainer's own fp32 arithmetic. Returns
+        (predicted poses (N,T',66) or None, MSE against `poses` as a fresh device
+        scalar or None). Changes no trainer state."""
+        x = keypoints_3d.contiguous()
+        y = None if poses is None else poses.contiguous()
+        _lib.require_gpu(x, y)   # on the device (RuntimeError), float32 (TypeError): the kernels read fp32
+        if x.dim() != 4 or x.shape[2:] != (17, 3):
+            raise ValueError(f"expected (N,T,17,3) keypoints, got {tuple(x.shape)}")
+        N, T = x.shape[:2]
+        lib = _lib.load()
+        To = _lib.check(lib.tik_trainer_out_frames(self._h.h, T)) if T > 0 else 0
+        if y is not None and tuple(y.shape) != (N, To, self.regressor.pose_dim):
+            raise ValueError(f"expected target poses {(N, To, self.regressor.pose_dim)}, got {tuple(y.shape)}")
+        out = torch.empty((N, To, self.regressor.pose_dim), device=x.device, dtype=torch.float32) if want_poses else None
+        loss = torch.empty((), device=x.device, dtype=torch.float32) if y is not None else None
+        if N == 0 or T == 0:
+            if loss is not None:
+                loss.fill_(float("nan"))   # the mean over no elements, as nn.MSELoss gives
+            return out, loss
+        _lib.check(lib.tik_trainer_eval(self._h.h, x.data_ptr(), N, T, _lib.ptr(y), _lib.ptr(out), _lib.ptr(loss),
+                                        _lib.stream_of(x)), "GpuTrainer.evaluate")
+        return out, loss
+
+    def predict(self, keypoints_3d: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """IKPoseTrainer.forward in eval mode on the weights being trained -> {"poses": (N,T',66)}."""
+        return {"poses": self.evaluate(keypoints_3d)[0]}
+
+    def validation_step(self, batch: Dict[str, torch.Tensor], batch_idx: int = 0):
+        """pose_trainer.py:158-164; the loss is a fresh device scalar each call."""
+        _, lss = self.evaluate(batch["keypoints_3d"].to(self.device), batch["poses"].to(self.device), want_poses=False)
+        return {"val_loss": lss, "pose_mse": lss}
+
+    def validation_epoch_end(self, outputs):
+        """pose_trainer.py:166-172: the mean of the batch means."""
+        losses = calc_mean_losses(outputs, ["pose_mse", "val_loss"])
+        return {"val_loss": losses["val_loss"], "log": {f"val/{k}": v for k, v in losses.items()}}
+
+    def validate(self, val_ds, batch_size: int):
+        """One pass over `val_ds` in dataset order -> validation_epoch_end's dict."""
+        n = len(val_ds)
+        outs = [self.validation_step(val_ds.get_batch(np.arange(lo, min(lo + batch_size, n))), b)
+                for b, lo in enumerate(range(0, n, batch_size))]
+        return self.validation_epoch_end(outs)
+
+    # ------------------------------------------------------------------ checkpoints
+    def _param_order(self):
+        """regressor.named_parameters() order: the index of torch.optim.Adam's state."""
+        return [n for n, _ in self.regressor.named_parameters()]
+
+    def save_checkpoint(self, path, epoch: int, **extra) -> str:
+        """A `.ckpt` that IKPoseTrainer.load_from_checkpoint and `from_checkpoint` read
+        (plain tensors and containers: torch.load(weights_only=True) accepts it):
+        epoch, global_step, state_dict (`regressor.` keys, BatchNorm counters
+        included), hparams (a dict), optimizer_states = [torch.optim.Adam.state_dict()
+        layout], plus `extra` (fit stores val_loss)."""
+        steps = self.steps
+        names = self._param_order()
+        hp = getattr(self, "hparams", None)
+        hpd = {k: v for k, v in (vars(hp) if hp is not None else {}).items()
+               if isinstance(v, (bool, int, float, str, type(None)))}
+        hpd["lr"] = self.lr
+        state = {i: {"step": torch.tensor(float(steps), dtype=torch.float32),
+                     "exp_avg": self.tensor(n, "exp_avg").cpu(), "exp_avg_sq": self.tensor(n, "exp_avg_sq").cpu()}
+                 for i, n in enumerate(names)}
+        group = {"lr": self.lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0, "amsgrad": False,
+                 "params": list(range(len(names)))}
+        ck = {"epoch": int(epoch), "global_step": int(steps),
+              "state_dict": {"regressor." + k: v.cpu() for k, v in self.state_dict().items()},
+              "hparams": hpd, "optimizer_states": [{"state": state, "param_groups": [group]}]}
+        ck.update(extra)
+        os.makedirs(os.path.dirname(os.path.abspath(str(path))), exist_ok=True)
+        torch.save(ck, str(path))
+        return str(path)
+
+    def _restore(self, path, device) -> dict:
+        """Rebuild this trainer from a checkpoint: weights and running statistics
+        (IKPoseTrainer.load_from_checkpoint), both Adam moments, steps and lr. A file
+        without optimizer_states gives fresh Adam state and steps = 0.
+
+        This re-runs __init__ on `self`: the device handle, `regressor`, `hparams`
+        and `lr` become the checkpoint's, as Lightning's resume_from_checkpoint
+        replaces the module's and the optimizer's state. The file is read twice
+        (by load_from_checkpoint for the model, here for the optimizer state),
+        with the allow-list load_from_checkpoint has already registered."""
+        model = IKPoseTrainer.load_from_checkpoint(str(path))
+        ck = torch.load(str(path), map_location="cpu", weights_only=True)
+        opt = (ck.get("optimizer_states") or [None])[0]
+        lr = float(opt["param_groups"][0]["lr"]) if opt else None
+        GpuTrainer.__init__(self, model, lr=lr, device=device)
+        if opt:
+            for i, n in enumerate(self._param_order()):
+                st = opt["state"].get(i)
+                if st is None:
+                    continue
+                self.write_tensor(n, st["exp_avg"].to(self.device, torch.float32), "exp_avg")
+                self.write_tensor(n, st["exp_avg_sq"].to(self.device, torch.float32), "exp_avg_sq")
+            steps = int(ck.get("global_step", 0))
+            _lib.check(_lib.load().tik_trainer_set_steps(self._h.h, steps), "from_checkpoint")
+            # the saved counters already include these steps; state_dict() adds `steps` again
+            self._nbt0 = {k: v - steps for k, v in self._nbt0.items()}
+        return ck
+
+    @classmethod
+    def from_checkpoint(cls, path, device="cuda") -> "GpuTrainer":
+        """A trainer that continues where `save_checkpoint` stopped."""
+        tr = cls.__new__(cls)
+        tr._restore(path, device)
+        return tr
+
+    # ------------------------------------------------------------------ fit
+    def fit(self, train_ds, val_ds=None, *, max_epochs: int, batch_size: int, ckpt_dir=None, save_top_k: int = 30,
+            resume_ckpt=None, shuffle_seed: int = 0) -> List[dict]:
+        """The Lightning loop of pose_trainer.py:233-256 without Lightning.
+
+        Per epoch: the train set in a permutation drawn from
+        RandomState(shuffle_seed * 1000003 + epoch) (a function of the epoch alone, so
+        a resumed run draws the same batches), batches from `ds.get_batch`; then
+        validation in dataset order, `checkpoint_epoch={e}-val_loss={v:.2f}.ckpt`
+        under `ckpt_dir` (the `save_top_k` lowest val_loss stay; < 0 keeps all, 0
+        writes none), then `train_ds.on_epoch_end(e)` (:174-177). Without `val_ds`
+        val_loss is the epoch's mean train loss. `resume_ckpt` (epoch e) restores
+        this trainer in place (weights, Adam state, steps, and `lr` / `hparams` /
+        `regressor` from the file: see `_restore`), counts the checkpoints of epochs
+        <= e already in `ckpt_dir` toward `save_top_k`, and continues at e + 1;
+        `max_epochs` counts from epoch 0.
+        Returns one {"epoch", "train/pose_mse", "val_loss", "ckpt"} per epoch run."""
+        start, kept = 0, []
+        ckpt_dir = None if ckpt_dir is None else str(ckpt_dir)
+        if resume_ckpt:
+            ck = self._restore(resume_ckpt, self.device)
+            e = int(ck["epoch"])
+            train_ds.on_epoch_end(e)
+            start = e + 1
+            # the interrupted run's files count toward save_top_k: earlier epochs by the
+            # val_loss in their names, the resume file by the exact value it stores
+            if ckpt_dir and os.path.isdir(ckpt_dir):
+                here = os.path.abspath(str(resume_ckpt))
+                for f in sorted(os.listdir(ckpt_dir)):
+                    m = _CKPT_NAME.match(f)
+                    p = os.path.join(ckpt_dir, f)
+                    if not m or int(m.group(1)) > e:
+                        continue
+                    exact = os.path.abspath(p) == here and "val_loss" in ck
+                    kept.append((float(ck["val_loss"]) if exact else float(m.group(2)), int(m.group(1)), p))
+        history = []
+        for epoch in range(start, int(max_epochs)):
+            n = len(train_ds)
+            perm = np.random.RandomState(int(shuffle_seed) * 1000003 + epoch).permutation(n)
+            losses = [self.training_step(train_ds.get_batch(perm[lo:lo + batch_size]), b)["loss"]
+                      for b, lo in enumerate(range(0, n, batch_size))]
+            if not losses:
+                raise ValueError("fit: the training set is empty")
+            train_loss = float(torch.stack(losses).mean())
+            val_loss = train_loss
+            if val_ds is not None and len(val_ds):
+                val_loss = float(self.validate(val_ds, batch_size)["val_loss"])
+            path = None
+            if ckpt_dir and save_top_k != 0:
+                path = self.save_checkpoint(os.path.join(ckpt_dir, f"checkpoint_epoch={epoch}-val_loss={val_loss:.2f}.ckpt"),
+                                            epoch, val_loss=val_loss)
+                kept.append((val_loss, epoch, path))
+                if save_top_k > 0 and len(kept) > save_top_k:
+                    kept.sort(key=lambda r: (r[0], r[1]))
+                    for _, _, p in kept[save_top_k:]:
+                        if os.path.exists(p):
+                            os.remove(p)
+                        if p == path:
+                            path = None
+                    kept = kept[:save_top_k]
+            train_ds.on_epoch_end(epoch)
+            history.append({"epoch": epoch, "train/pose_mse": train_loss, "val_loss": val_loss, "ckpt": path})
+        return history
+
+
+def calc_mean_losses(outputs, loss_keys):
+    """pose_trainer.py:27-39: per key, the mean over the outputs that have it; keys no
+    output has are left out."""
+    sums = {k: 0.0 for k in loss_keys}
+    cnts = {k: 0 for k in loss_keys}
+    for out in outputs:
+        for k in loss_keys:
+            if k in out:
+                sums[k] = sums[k] + out[k]
+                cnts[k] += 1
+    return {k: sums[k] / cnts[k] for k in loss_keys if cnts[k] > 0}
+
+
+# ---------------------------------------------------------------------- CLI
+def _load_amass_path_list(csv_file):
+    """pose_trainer.py:20-24: one sequence path per line."""
+    with open(csv_file, "r") as fh:
+        return [Path(ll.strip()) for ll in fh.readlines() if ll.strip()]
+
+
+def build_parser() -> argparse.ArgumentParser:
+    """The reference's training arguments and defaults (pose_trainer.py:204-230)."""
+    p = argparse.ArgumentParser(prog="python -m temporal_inverse_kinematics_amd.trainer")
+    p.add_argument("--amass", type=str, default="/media/F/datasets/amass", help="amass dir")
+    p.add_argument("--data_dir", type=str, default="/media/F/datasets/amass/ik_model", help="data dir")
+    p.add_argument("--n_workers", type=int, default=8, help="accepted and ignored (batches are built on the device)")
+    p.add_argument("--max_epoch", type=int, default=200, help="max epoch")
+    p.add_argument("--smpl_mean", type=str, default="/media/F/thesis/motion_capture/data/smpl/smpl_mean_params.npz",
+                   help="accepted and ignored, as in the reference")
+    p.add_argument("--n_train", type=int, default=-1, help="use the first n training sequences (-1: all)")
+    p.add_argument("--n_valid", type=int, default=-1, help="use the first n validation sequences (-1: all)")
+    p.add_argument("--resume_ckpt", type=str, default="", help="checkpoint to continue from")
+    p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--win_size", default=9, type=int, help="window size in frames")
+    p.add_argument("--bs", default=256, type=int, help="batch size in terms of predicted frames")
+    p.add_argument("--kps_channel", default=3, type=int, help="keypoint channel")
+    p.add_argument("--graph_layout", default="coco", type=str, choices=["coco", "openpose"], help="skeleton graph layout")
+    p.add_argument("--max_hop", default=2, type=int, help="graph max hop")
+    p.add_argument("--dilation", default=1, type=int, help="conv dilation")
+    p.add_argument("--keypoint_format", default="coco", type=str, help="input model keypoint format")
+    p.add_argument("--n_out_joints", default=22, type=int, help="number of output joints")
+    p.add_argument("--n_out_channels", default=3, type=int, help="number of output channels")
+    p.add_argument("--synthetic_smplx", action="store_true",
+                   help="use the seeded synthetic SMPL-X constants instead of <amass>/smplx (tests, dry runs)")
+    return p
+
+
+def run_train(argv=None) -> int:
+    """pose_trainer.py:233-256: train.csv / valid.csv under --data_dir, SMPL-X models
+    from <amass>/smplx, the shape DB <amass>/smplx_shapes.npz for the training set
+    only, checkpoints (top 30) under <data_dir>/model_ckps/."""
+    from .smplx_fk import load_smplx_models
+    from .training_data import AmassDataset
+    hp = build_parser().parse_args(argv)
+    data_dir = Path(hp.data_dir)
+    train_paths = _load_amass_path_list(data_dir / "train.csv")
+    val_paths = _load_amass_path_list(data_dir / "valid.csv")
+    if hp.n_train > 0:
+        train_paths = train_paths[:hp.n_train]
+    if hp.n_valid > 0:
+        val_paths = val_paths[:hp.n_valid]
+    shape_path = Path(hp.amass) / "smplx_shapes.npz"
+    if not shape_path.exists():
+        raise FileNotFoundError(f"smplx_shapes.npz is not found under {hp.amass}")
+    smplx = load_smplx_models(None if hp.synthetic_smplx else Path(hp.amass) / "smplx", "cuda", batch_size=1024)
+    train_ds = AmassDataset(smplx_models=smplx, amass_paths=train_paths, window_size=hp.win_size,
+                            keypoint_format=hp.keypoint_format, shape_db_path=shape_path)
+    val_ds = AmassDataset(smplx_models=smplx, amass_paths=val_paths, window_size=hp.win_size,
+                          keypoint_format=hp.keypoint_format)
+    tr = GpuTrainer(IKPoseTrainer(hp))
+    if hp.resume_ckpt:
+        print(f"resume from checkpoint: {hp.resume_ckpt}")
+    else:
+        print("start new training with new model weights")
+    history = tr.fit(train_ds, val_ds, max_epochs=hp.max_epoch, batch_size=hp.bs, ckpt_dir=data_dir / "model_ckps",
+                     save_top_k=30, resume_ckpt=hp.resume_ckpt or None)
+    for row in history:
+        print(json.dumps(row))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(run_train())
