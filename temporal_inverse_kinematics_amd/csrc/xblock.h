@@ -33,9 +33,11 @@ struct XBlkArgs {
 };
 
 // raw: block 0 from the keypoints (writes P3); else block 1 from P3 (writes fp32).
-// One 512-thread workgroup per CU (ncu), persistent over tiles of 10 output frames.
+// One 512-thread workgroup per CU (ncu), persistent over tiles of 10 output frames
+// (block 1) or 14 (block 0, which keeps no x image in LDS).
 hipError_t launch_xblock(const XBlkArgs& a, bool raw, int ncu, hipStream_t st);
-int xblock_frames_per_tile();
+int xblock_frames_per_tile();    // block 1
+int xblock0_frames_per_tile();   // block 0
 // fp32 weights w[co][tap * cin + ci] (row stride ldw) -> bf16x3 planes in the
 // MFMA A-operand register layout [co/16][tap * cin/32 + kb][plane][lane][8]
 std::vector<unsigned short> xblock_pack_weights(const float* w, int cout, int ldw, int kt, int cin);

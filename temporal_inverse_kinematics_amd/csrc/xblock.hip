@@ -3,8 +3,9 @@
 //
 // Layered, a block is two launches: G (x -> z) and T (z, x -> out), five
 // activation streams through HBM (read x, write z, read z + taps, read x,
-// write out). Here one persistent workgroup per CU walks tiles of F = 10
-// output frames (12 input frames: one halo frame each side for the taps):
+// write out). Here one persistent workgroup per CU walks tiles of F output
+// frames (F + 2 input frames: one halo frame each side for the taps), F = 10
+// in block 1 and 14 in block 0:
 //   block 0 (RAW): z0 = ReLU(mix(data_bn(keypoints) . Wg0') + bias2) in fp32
 //     VALU (layer0.hip's gcn0 arithmetic) straight into the LDS z image;
 //   block 1: G = x . Wg1' on MFMA from an LDS x image of the tile's 12 input
@@ -39,17 +40,22 @@ namespace tik {
 namespace xb {
 constexpr int V = 17, C = 64, F = 10, FIN = F + 2;
 constexpr int ROWB = 3 * C * 2;                        // 384 B per P3 row
-constexpr int ZROWS = FIN * V, ZR = ZROWS;             // z image rows + the zero row
+constexpr int ZROWS = FIN * V;                         // z image rows (+ the zero row)
 constexpr int ZBYTES = (ZROWS + 1) * ROWB;             // 78,720
 constexpr int XUNITS = ZROWS * 24, XINST = (XUNITS + 63) / 64;   // 16-B units of the x image, DMA instructions
 constexpr int XBYTES = XINST * 1024;                   // 78,848 (padded to whole DMA instructions)
 constexpr int B2BYTES = V * C * 4;                     // bias2 for the mix
-constexpr int KPBYTES = FIN * V * 4 * 4;               // RAW: data_bn'd keypoints, 4 floats per pixel
 constexpr int SMEM1 = ZBYTES + XBYTES + B2BYTES;       // block 1
-constexpr int UBYTES = FIN * V * 16;                   // RAW: the mixed keypoints u[f][w] (4 floats)
-constexpr int SMEM0 = ZBYTES + KPBYTES + UBYTES;       // block 0
-constexpr int TPX = F * V, TBLK = (TPX + 15) / 16;     // 170 output pixels in 11 blocks of 16
-static_assert(SMEM1 <= 163840, "LDS");
+// block 0 has no x image, so its tile is 14 output frames (16 input frames): every one
+// of the 16 frame lanes of its VALU gcn is live (12 of 16 at F = 10), T covers 238
+// pixels in 15 blocks (99 % full against 96.6 %), the halo is 16/14 instead of 12/10
+// and there are fewer tiles, so fewer per-tile barriers
+constexpr int F0 = 14, FIN0 = F0 + 2;
+constexpr int ZBYTES0 = (FIN0 * V + 1) * ROWB;         // 104,832
+constexpr int KPBYTES0 = FIN0 * V * 4 * 4;             // data_bn'd keypoints, 4 floats per pixel
+constexpr int UBYTES0 = FIN0 * V * 16;                 // the mixed keypoints u[f][w] (4 floats)
+constexpr int SMEM0 = ZBYTES0 + KPBYTES0 + UBYTES0;    // block 0: 113,536
+static_assert(SMEM1 <= 163840 && SMEM0 <= 163840, "LDS");
 }  // namespace xb
 
 // unit u (16 B: 8 channels of one plane segment) of P3 image row R sits at u ^ (R & 7)
@@ -63,6 +69,11 @@ __device__ __forceinline__ int xb_xunit(int R, int j, int plane, int u) { return
 template <bool RAW>
 __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
     using namespace xb;
+    // the tile of this block (these hide xb's block 1 values)
+    constexpr int F = RAW ? F0 : xb::F, FIN = F + 2, ZROWS = FIN * V, ZR = ZROWS, ZBYTES = (ZROWS + 1) * ROWB;
+    constexpr int KPBYTES = FIN * V * 4 * 4;                 // block 0: bytes of the keypoint image
+    constexpr int TPX = F * V, TBLK = (TPX + 15) / 16;       // block 1: 170 output pixels in 11 blocks of 16; block 0: 238 in 15
+    static_assert(FIN <= 16, "one frame per lane of a 16-lane group");
     __shared__ __attribute__((aligned(16))) unsigned char smem[RAW ? SMEM0 : SMEM1];
     unsigned char* const zimg = smem;
     unsigned char* const ximg = smem + ZBYTES;            // block 1: x image; block 0: keypoint image
@@ -188,8 +199,8 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
         issue_x(t_begin);
     }
 
-    // T: this wave's output pixel blocks (ph 0: blocks 0-5, ph 1: 6-10)
-    constexpr int NB = (TBLK + 1) / 2;   // 6
+    // T: this wave's output pixel blocks (block 1: ph 0 blocks 0-5, ph 1 6-10; block 0: 0-7, 8-14)
+    constexpr int NB = (TBLK + 1) / 2;   // 6 (block 0: 8)
     const int blk0 = ph * NB;
     const int nblk = ph == 0 ? NB : TBLK - NB;
 
@@ -221,7 +232,7 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
         asm volatile("" : "+v"(tid), "+v"(lane));
         g = lane >> 4;
         cho = 16 * cg + 4 * g;
-        // ================= 1. z image of the tile's 12 input frames
+        // ================= 1. z image of the tile's input frames
         if constexpr (RAW) {
             // data_bn(keypoints) -> keypoint image (the previous tile's T finished reading it)
             float* kps = reinterpret_cast<float*>(ximg);
@@ -500,7 +511,8 @@ hipError_t launch_xblock(const XBlkArgs& a, bool raw, int ncu, hipStream_t st) {
         return hipErrorInvalidValue;
     if (!raw && (!a.xp3 || !a.wgp || !a.bias2 || !a.out_f)) return hipErrorInvalidValue;
     if (!raw && (long long)a.nframes * xb::V * xb::ROWB >= (1LL << 31)) return hipErrorInvalidValue;   // 32-bit DMA offsets
-    const int ntiles = (a.nframes + xb::F - 1) / xb::F;
+    const int f = raw ? xb::F0 : xb::F;
+    const int ntiles = (a.nframes + f - 1) / f;
     const int grid = std::min(ntiles, ncu);
     (void)hipGetLastError();
     if (raw) hipLaunchKernelGGL(xblock_kernel<true>, dim3(grid), dim3(512), 0, st, a);
@@ -509,6 +521,7 @@ hipError_t launch_xblock(const XBlkArgs& a, bool raw, int ncu, hipStream_t st) {
 }
 
 int xblock_frames_per_tile() { return xb::F; }
+int xblock0_frames_per_tile() { return xb::F0; }
 
 std::vector<unsigned short> xblock_pack_weights(const float* w, int cout, int ldw, int kt, int cin) {
     // [cg][tap * (cin/32) + kb][plane][lane][8]: lane l = channel 16 cg + (l & 15), K = 32 kb + 8 (l >> 4) + e
