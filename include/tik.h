@@ -48,6 +48,15 @@ const char* tik_version(void);
 // 1 MiB guard zones; returns the number of written guard zones (description
 // in tik_last_error(), guards re-armed), or < 0 on error.
 int tik_debug_check_guards(void);
+// Debug: with TIK_POISON=<two hex digits> in the environment (read at every
+// allocation, so it may be set after the library is loaded) the payload of
+// every new library buffer is filled with that byte before it is returned;
+// with TIK_GUARD=1 as well the guard zones keep 0xA5. ff = NaN as fp32 and as
+// bf16, -1 as int; 7f = 3.39e38 as fp32 and as bf16, finite, so it survives a
+// `s > 0 ? s : 0` ReLU, which flushes NaN to 0. Any other spelling fails the
+// allocation with TIK_E_INVALID. tik_debug_alloc_fill returns the fill byte
+// of the most recent allocation, or -1 (none yet, or it was not filled).
+int tik_debug_alloc_fill(void);
 // Debug: with TIK_CHECKSUM set, every launch of the IK forward is followed by
 // a synchronising checksum of its output; copies "label:hex;..." of the
 // launches since the last call into buf and clears the record.

@@ -33,6 +33,7 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_last_error": (ctypes.c_char_p, ()),
     "tik_version": (ctypes.c_char_p, ()),
     "tik_debug_check_guards": (_I, ()),
+    "tik_debug_alloc_fill": (_I, ()),
     "tik_debug_checksums": (_I, (ctypes.c_char_p, _I)),
     "tik_model_create": (_I, (ctypes.POINTER(TikTensor), _I, ctypes.POINTER(_P))),
     "tik_model_destroy": (_I, (_P,)),

@@ -33,6 +33,7 @@
 
 namespace tik_host {
 thread_local std::string g_err;
+std::atomic<int> g_alloc_fill{-1};
 
 bool guard_mode() {
     static const bool on = getenv("TIK_GUARD") && getenv("TIK_GUARD")[0] == '1';
@@ -548,7 +549,13 @@ int tik_debug_check_guards(void) {
             const char* gp = side == 0 ? base : base + GUARD_BYTES + kv.second;
             HIP_TRY(hipMemcpy(h.data(), gp, GUARD_BYTES, hipMemcpyDeviceToHost));
             size_t first = GUARD_BYTES, last = 0, cnt = 0;
-            for (size_t i = 0; i < GUARD_BYTES; ++i)
+            bool clean = true;   // the common case, a word at a time (a handle has hundreds of guards)
+            for (size_t i = 0; i < GUARD_BYTES && clean; i += 8) {
+                unsigned long long w;
+                memcpy(&w, h.data() + i, 8);
+                clean = w == 0xA5A5A5A5A5A5A5A5ull;
+            }
+            for (size_t i = 0; i < GUARD_BYTES && !clean; ++i)
                 if (h[i] != 0xA5) { first = std::min(first, i); last = i; ++cnt; }
             if (cnt) {
                 ++bad;
@@ -563,6 +570,7 @@ int tik_debug_check_guards(void) {
     g_err = rep;
     return bad;
 }
+int tik_debug_alloc_fill(void) { return g_alloc_fill.load(); }
 const char* tik_version(void) { return "tik 0.4.0 (gfx950; bf16x3 split MFMA (default, fp32 range), exact fp32 MFMA)"; }
 
 int tik_model_create(const tik_tensor* tensors, int n_tensors, tik_model_t* out) {

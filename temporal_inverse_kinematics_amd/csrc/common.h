@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -75,16 +76,50 @@ bool guard_mode();
 void guard_register(void* base, size_t bytes);
 void guard_unregister(void* base);
 
-inline hipError_t dev_alloc(void** p, size_t bytes) {
-    if (!guard_mode()) return hipMalloc(p, bytes);
+// Debug hook (TIK_POISON=<two hex digits>): the payload of every new device
+// buffer is filled with that byte (ff = NaN as fp32 and bf16, -1 as int;
+// 7f = 3.39e38, finite, so it survives a ReLU that flushes NaN), so a kernel
+// that reads memory it never wrote shows in its output. Read on every
+// allocation (not latched): workspaces grow lazily inside the forward calls.
+// -1 = unset, -2 = malformed (g_err set).
+extern std::atomic<int> g_alloc_fill;   // fill byte of the last allocation, or -1 (tik_debug_alloc_fill)
+inline int poison_from_env() {
+    const char* e = getenv("TIK_POISON");
+    if (!e) return -1;
+    auto hex = [](char c) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10
+                                 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; };
+    if (strlen(e) != 2 || hex(e[0]) < 0 || hex(e[1]) < 0) {
+        fail(TIK_E_INVALID, "TIK_POISON=%s: expected two hex digits (e.g. ff or 7f)", e);
+        return -2;
+    }
+    return hex(e[0]) * 16 + hex(e[1]);
+}
+
+// -> TIK_OK or a TIK_E_* code with the message set. The fills are followed by
+// a device synchronise: the buffer's users run on non-blocking streams, which
+// a hipMemset on the legacy stream does not order against.
+inline int dev_alloc(void** p, size_t bytes) {
+    const int fill = poison_from_env();
+    if (fill == -2) return TIK_E_INVALID;
+    const bool guard = guard_mode();
+    const size_t g = guard ? GUARD_BYTES : 0;
     char* base = nullptr;
-    const size_t tot = bytes + 2 * GUARD_BYTES;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), tot);
-    if (e != hipSuccess) return e;
-    if ((e = hipMemset(base, 0xA5, tot)) != hipSuccess) return e;
-    guard_register(base, bytes);
-    *p = base + GUARD_BYTES;
-    return hipSuccess;
+    if (hipMalloc(reinterpret_cast<void**>(&base), bytes + 2 * g) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(TIK_E_NOMEM, "hipMalloc(%zu bytes) failed", bytes + 2 * g);
+    }
+    hipError_t e = hipSuccess;
+    if (guard) e = hipMemset(base, 0xA5, bytes + 2 * g);
+    if (e == hipSuccess && fill >= 0 && bytes) e = hipMemset(base + g, fill, bytes);
+    if (e == hipSuccess && (guard || fill >= 0)) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(base);
+        return fail(TIK_E_HIP, "dev_alloc: fill of %zu bytes failed: %s", bytes + 2 * g, hipGetErrorString(e));
+    }
+    if (guard) guard_register(base, bytes);
+    g_alloc_fill = fill;
+    *p = base + g;
+    return TIK_OK;
 }
 inline void dev_free(void* p) {
     if (!p) return;
@@ -114,7 +149,7 @@ struct DevArray {   // owning device buffer; move-only (a copy would double-free
         dev_free(p); p = nullptr;
         n = h.size();
         if (n == 0) return TIK_OK;
-        if (dev_alloc(reinterpret_cast<void**>(&p), n * sizeof(T)) != hipSuccess) { n = 0; return fail(TIK_E_NOMEM, "hipMalloc(%zu elements) failed", h.size()); }
+        if (const int rc = dev_alloc(reinterpret_cast<void**>(&p), n * sizeof(T))) { p = nullptr; n = 0; return rc; }
         if (hipMemcpy(p, h.data(), n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
             return fail(TIK_E_HIP, "hipMemcpy H2D failed");
         return TIK_OK;
@@ -122,7 +157,7 @@ struct DevArray {   // owning device buffer; move-only (a copy would double-free
     int reserve(size_t want) {
         if (want <= n) return TIK_OK;
         dev_free(p); p = nullptr;
-        if (dev_alloc(reinterpret_cast<void**>(&p), want * sizeof(T)) != hipSuccess) { n = 0; return fail(TIK_E_NOMEM, "hipMalloc(%zu elements) failed", want); }
+        if (const int rc = dev_alloc(reinterpret_cast<void**>(&p), want * sizeof(T))) { p = nullptr; n = 0; return rc; }
         n = want;
         return TIK_OK;
     }
