@@ -1,12 +1,15 @@
 """Config #4: SMPL-X full 55-joint FK + 10475-vertex LBS, batch=4096, 1 GPU.
 
-    python bench_fk.py [--batch 4096] [--steps 10] [--warmup 20]
+    python bench_fk.py [--batch 4096] [--steps 10] [--warmup 20] [--joints {all,coco}]
 
 Prints one JSON line: bodies/s, and per kernel (HIP events around every launch
 of a second pass of the same steps, tik_fk_profile) the algorithmic TFLOP/s of
 the blend-shape and skinning GEMMs against the bf16x3 MFMA roof and the
 vertex bytes over HBM; then the oracle CPU baseline. bench.py --full reuses
-measure_fk() for its "fk" key.
+measure_fk() for its "fk" key. --joints adds a "joints" key: the mesh-free
+SMPLX.joints (all 144 joints, or the COCO-17 selection) against
+full_forward(return_verts=False) at the same batch, the two legs alternating
+in this process.
 """
 import argparse, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -84,15 +87,89 @@ def measure_fk(batch=4096, steps=10, warmup=20):
                      f"({BF16_MFMA_PEAK_TFLOPS} TF dense bf16 / 6 products); vertex_gbs = vertex bytes written / step time"}
 
 
+def _profile(m, run, steps):
+    """Per-label HIP-event averages of `steps` calls of run() (tik_fk_profile)."""
+    import torch
+    from temporal_inverse_kinematics_amd import _lib
+    lib = _lib.load()
+    _lib.check(lib.tik_fk_profile(m._h, 8 * steps))
+    for _ in range(steps):
+        run()
+    torch.cuda.synchronize()
+    agg = {}
+    lab = ctypes.create_string_buffer(64)
+    kms, fl, by = ctypes.c_float(), ctypes.c_double(), ctypes.c_double()
+    for i in range(_lib.check(lib.tik_fk_profile_count(m._h))):
+        _lib.check(lib.tik_fk_profile_read(m._h, i, lab, 64, ctypes.byref(kms), ctypes.byref(fl), ctypes.byref(by)))
+        a = agg.setdefault(lab.value.decode(), [0.0, 0, 0.0, 0.0])
+        a[0] += kms.value; a[1] += 1; a[2] += fl.value; a[3] += by.value
+    lib.tik_fk_profile(m._h, 0)
+    tot = sum(v[0] for v in agg.values())
+    return {k: {"avg_ms": round(t / n, 4), "share": round(t / tot, 3), "gflops": round(f / (t / 1e3) / 1e9, 1),
+                "gbs": round(b / (t / 1e3) / 1e9, 1)} for k, (t, n, f, b) in agg.items()}
+
+
+def measure_joints(select="all", batch=4096, steps=10, warmup=20, rounds=5):
+    """SMPLX.joints (select: "all" or "coco") against full_forward(return_verts=False)
+    at `batch` bodies, outputs preallocated, inputs resident: `rounds` rounds, each
+    timing `steps` calls of one leg and then of the other (HIP events), the median
+    round per leg. The joints handle is a fresh one, so its workspace is the joints
+    path's alone."""
+    import statistics
+    import torch
+    from temporal_inverse_kinematics_amd import _build, synthetic as syn
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    _build.build()
+    c = syn.synthetic_smplx_constants(seed=1)
+    mj, mf = SMPLX(c, batch_size=batch), SMPLX(c, batch_size=batch)
+    pose, betas = syn.synthetic_fk_inputs(batch, seed=1)
+    P, Bt = torch.from_numpy(pose).cuda(), torch.from_numpy(betas).cuda()
+    sel = None if select == "all" else select
+    n = mj.num_joints if sel is None else 17
+    oj = torch.empty((batch, n, 3), device="cuda")
+    of = (torch.empty((batch, mf.num_joints, 3), device="cuda"), None)
+    legs = {"joints": lambda: mj.joints(P, Bt, select=sel, out=oj),
+            "full_forward": lambda: mf.full_forward(P, Bt, return_verts=False, out=of)}
+    for _ in range(warmup):
+        for run in legs.values():
+            run()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, run in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(steps):
+                run()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / steps)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    ws = mj.workspace_bytes
+    return {"select": select, "n_joints": n, "batch": batch, "steps": steps, "warmup": warmup, "rounds": rounds,
+            "joints_ms": round(med["joints"], 4), "full_forward_ms": round(med["full_forward"], 4),
+            "ratio": round(med["full_forward"] / med["joints"], 2),
+            "joints_ms_rounds": [round(v, 4) for v in ms["joints"]],
+            "full_forward_ms_rounds": [round(v, 4) for v in ms["full_forward"]],
+            "workspace_bytes": ws, "full_forward_workspace_bytes": mf.workspace_bytes,
+            "kernels": _profile(mj, legs["joints"], steps),
+            "basis": "median of rounds, each `steps` calls per leg between HIP events, legs alternating; "
+                     "full_forward(return_verts=False) builds the body in the handle's workspace"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--joints", choices=["all", "coco"], default=None,
+                    help="also time the mesh-free SMPLX.joints against full_forward(return_verts=False)")
     a = ap.parse_args()
     from temporal_inverse_kinematics_amd import synthetic as syn
     out = measure_fk(a.batch, a.steps, a.warmup)
+    if a.joints:
+        out["joints"] = measure_joints(a.joints, a.batch, a.steps, a.warmup)
     from oracle import smplx_lbs as sl
     c = syn.synthetic_smplx_constants(seed=1)
     pose, betas = syn.synthetic_fk_inputs(16, seed=1)

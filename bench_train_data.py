@@ -1,7 +1,7 @@
 """SURVEY.md §8f row 4 (data half): AmassDataset training-data generation on
 the GPU (temporal_inverse_kinematics_amd/training_data.py).
 
-    python bench_train_data.py [--seqs 64] [--frames 1000] [--batch 4096] [--steps 50]
+    python bench_train_data.py [--seqs 64] [--frames 1000] [--batch 4096] [--steps 50] [--mesh-free]
 
 Workload: synthetic AMASS-shaped sequences (156 pose columns, random betas,
 three genders) on the seeded synthetic SMPL-X constants; window 64 (65
@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--mesh-free", action="store_true",
+                    help="AmassDataset(mesh_free=True): the per-epoch FK takes the 17 target joints only, no mesh")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -41,7 +43,8 @@ def main():
         seqs.append({"poses": poses, "betas": rng.normal(0, 1, 10).astype(np.float32),
                      "gender": ["male", "female", "neutral"][i % 3]})
     models = load_smplx_models(None, "cuda", batch_size=9)
-    ds = AmassDataset(models, seqs, window_size=64, keypoint_format="coco", add_gaussian_noise=True)
+    ds = AmassDataset(models, seqs, window_size=64, keypoint_format="coco", add_gaussian_noise=True,
+                      mesh_free=a.mesh_free)
     # per-epoch regeneration
     torch.cuda.synchronize()
     reps = 3
@@ -63,12 +66,23 @@ def main():
     out = {"metric": "AmassDataset training items/s (window 64, noise)", "value": round(a.batch / dt, 1),
            "unit": "items/s", "ms_per_batch": round(dt * 1e3, 4), "batch": a.batch, "n_gpus": 1,
            "regen_frames_per_s": round(n / regen, 1), "regen_ms_per_epoch": round(regen * 1e3, 3),
-           "dtype": "fp32 (FK: bf16x3 split MFMA, fp32 range)", "data": f"synthetic: {a.seqs} sequences x {a.frames} frames",
+           "fk_path": "mesh_free (SMPLX.joints, COCO-17 selection)" if a.mesh_free
+                      else "mesh (full_forward, return_verts=False)",
+           "fk_workspace_bytes": {g: m.workspace_bytes for g, m in models.items()},
+           "dtype": "fp32 (FK: fp32 FMAs on the picked vertices)" if a.mesh_free
+                    else "fp32 (FK: bf16x3 split MFMA, fp32 range)", "data": f"synthetic: {a.seqs} sequences x {a.frames} frames",
            "config": {"workload": "data_amass.AmassDataset: per-epoch root rotation + SMPL-X FK joints; "
                                   "items = COCO-17 window + noise + target pose"}}
     if not a.no_cpu_baseline:
         from oracle import amass as oa
-        joints = [d["keypoints_3d"].cpu().numpy() for d in ds.data_anims]
+        joints = []
+        for d in ds.data_anims:
+            j = d["keypoints_3d"].cpu().numpy()
+            if a.mesh_free:   # the oracle gathers from the SMPL-X joint slots
+                full = np.zeros((j.shape[0], 144, 3), np.float32)
+                full[:, ds.target_kps_mapping] = j
+                j = full
+            joints.append(j)
         poses = [d["poses"].cpu().numpy() for d in ds.data_anims]
         k, t0 = 0, time.perf_counter()
         while time.perf_counter() - t0 < 10.0:

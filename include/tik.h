@@ -300,8 +300,28 @@ int tik_fk_num_verts(tik_fk_t fk);
 int tik_fk_reserve(tik_fk_t fk, int B);
 int tik_fk_forward(tik_fk_t fk, const float* full_pose, const float* betas, const float* expression,
                    const float* transl, int B, float* joints, float* verts, void* stream);
+/* Joints of tik_fk_forward without the mesh. sel_host: n_sel joint indices in
+ * [0, tik_fk_num_joints) in output order (duplicates allowed), or NULL = all
+ * joints in order (n_sel ignored). out: (B, n_sel or njoints, 3) device fp32.
+ * Joints below 55 are the chain's, bit for bit those of tik_fk_forward. Every
+ * other joint is 1 or 3 vertices of the body, and only those are evaluated
+ * (blend shapes, skinning, barycentric sum; vertices no selected joint needs
+ * are skipped), in fp32 FMAs whose order is fixed: a body's joints are the
+ * same bits for any B, any place in the batch and any selection.
+ * tik_fk_set_precision does not change this path (fp32 FMAs in both settings;
+ * within 2e-4 of tik_fk_forward's joints). The selection (at most 256
+ * entries) travels in the kernel arguments: a call uploads nothing and is
+ * stream-ordered like tik_fk_forward. Workspace: 1337 floats per body (pose
+ * feature, transforms, chain joints); the mesh path's vertex buffers are never
+ * reserved. TIK_E_INVALID: null pointers, B <= 0, an index out of range,
+ * n_sel outside 1..256. */
+int tik_fk_joints(tik_fk_t fk, const float* full_pose, const float* betas, const float* expression,
+                  const float* transl, int B, const int* sel_host, int n_sel, float* out, void* stream);
+/* Bytes of device workspace the handle currently owns (constants excluded). */
+long long tik_fk_workspace_bytes(tik_fk_t fk);
 /* Per-launch HIP-event profile of tik_fk_forward (fk_chain, fk_blend, fk_skin,
- * fk_landmarks), as tik_model_profile / _count / _read. */
+ * fk_landmarks) and tik_fk_joints (fk_chain, fk_joints), as tik_model_profile /
+ * _count / _read. */
 int tik_fk_profile(tik_fk_t fk, int max_launches);
 int tik_fk_profile_count(tik_fk_t fk);
 int tik_fk_profile_read(tik_fk_t fk, int i, char* label, int label_len, float* ms, double* flops, double* bytes);

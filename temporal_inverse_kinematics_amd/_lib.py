@@ -72,6 +72,8 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_fk_num_verts": (_I, (_P,)),
     "tik_fk_reserve": (_I, (_P, _I)),
     "tik_fk_forward": (_I, (_P, _P, _P, _P, _P, _I, _P, _P, _P)),
+    "tik_fk_joints": (_I, (_P, _P, _P, _P, _P, _I, ctypes.POINTER(_I), _I, _P, _P)),
+    "tik_fk_workspace_bytes": (ctypes.c_longlong, (_P,)),
     "tik_fk_profile": (_I, (_P, _I)),
     "tik_fk_profile_count": (_I, (_P,)),
     "tik_fk_profile_read": (_I, (_P, _I, ctypes.c_char_p, _I, ctypes.POINTER(ctypes.c_float),

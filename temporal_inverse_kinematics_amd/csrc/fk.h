@@ -58,4 +58,36 @@ struct FkLmkArgs {
 hipError_t launch_fk_chain(const FkChainArgs& a, hipStream_t st);
 hipError_t launch_fk_landmarks(const FkLmkArgs& a, hipStream_t st);
 
+// Selected joints without the mesh (fk_joints.hip), after fk_chain_kernel wrote
+// feat, ajt, dyn_bin and the (B,55,3) chain joints. Output column s is joint
+// sel[s] (or s itself when sel_all). A joint below 55 is copied from jchain; any
+// other is 1 (vertex joint) or 3 (landmark) vertex evaluations in fp32 FMAs:
+//   v_posed[c] = sum_k feat[b][k] PT[3v+c][k]
+//   T = sum_j W[v][j] A_j(b)                             joints ascending (nzw entries, or all 55 of WT)
+//   x = T[:3,:3] v_posed + T[:,3];  joint = sum_i bary_i x_i + transl
+// one lane per body. The k sum is eight 64-k partial sums, each from zero and
+// ascending, added in order; the order of every sum is the same for any B,
+// body position and selection.
+constexpr int FKJ_MAX_SEL = 256;
+constexpr int FKJ_TB = 64;   // bodies per workgroup tile (lane = body)
+struct FkJointsArgs {
+    int B, n_out, nextra, nlmk, ndyn, nz, sel_all;   // nz: nzw entries per vertex (4, 8, 16) or 0 = dense WT
+    int split;               // set by the launcher: workgroup per column, wave = 64-k chunk (small launches)
+    const float* feat;       // (B,512)
+    const float* ajt;        // (55,B,12)
+    const float* jchain;     // (B,55,3) chain joints, transl included
+    const float* transl;     // (B,3) or null
+    const float* PT;         // [3V][512]
+    const float* WT;         // [V][64]
+    const int2* nzw;         // (V,nz) or null
+    const int* pick_v;       // (nextra+nlmk, 3) vertex ids of the static joints 55.. (a vertex joint uses entry 0)
+    const float* pick_w;     // (nextra+nlmk, 3) their barycentric weights (vertex joint: 1, 0, 0)
+    const int* dyn_v;        // (79, ndyn, 3) contour vertex ids by bin
+    const float* dyn_w;      // (79, ndyn, 3)
+    const int* dyn_bin;      // (B)
+    float* out;              // (B, n_out, 3)
+    unsigned short sel[FKJ_MAX_SEL];
+};
+hipError_t launch_fk_joints(const FkJointsArgs& a, hipStream_t st);
+
 }  // namespace tik

@@ -80,6 +80,10 @@ struct tik_fk {
     DevBuf zero_transl;   // (B,3) zeros: the skinning kernel always reads a translation
     DevIBuf dyn_bin;
     int cap = 0;
+    // tik_fk_joints (fk_joints.hip): per joint >= 55 its (vertex, barycentric weight) picks, the
+    // contour's by bin; workspace: the chain's (B,55,3) joints (feat, ajt, dyn_bin are shared)
+    DevIBuf pick_v, dyn_v;
+    DevBuf pick_w, jchain;
     Profiler prof;     // per-launch HIP events (tik_fk_profile; bench.py's FK roofline)
     bool profiling = false;
 };
@@ -254,6 +258,29 @@ int tik_fk_create(const tik_tensor* tensors, int n_tensors, int flags, tik_fk_t*
     if (fk->contour && ((rc = fk->dyn_faces.upload(hdf)) || (rc = fk->dyn_bary.upload(db->v)))) {
         delete fk;
         return rc;
+    }
+    {   // pick tables of the mesh-free joints path: vertex joints one pick of weight 1, landmarks three
+        const int ns = fk->nextra + fk->nlmk;
+        std::vector<int> pv((size_t)ns * 3, 0), dv;
+        std::vector<float> pw((size_t)ns * 3, 0.f);
+        for (int k = 0; k < fk->nextra; ++k) {
+            pv[3 * k] = hex[k];
+            pw[3 * k] = 1.0f;
+        }
+        for (int l = 0; l < fk->nlmk; ++l)
+            for (int i = 0; i < 3; ++i) {
+                pv[3 * (fk->nextra + l) + i] = hfaces[3 * hlf[l] + i];
+                pw[3 * (fk->nextra + l) + i] = lb->v[3 * l + i];
+            }
+        if (fk->contour) {
+            dv.resize(hdf.size() * 3);
+            for (size_t e = 0; e < hdf.size(); ++e)
+                for (int i = 0; i < 3; ++i) dv[3 * e + i] = hfaces[3 * hdf[e] + i];
+        }
+        if ((rc = fk->pick_v.upload(pv)) || (rc = fk->pick_w.upload(pw)) || (rc = fk->dyn_v.upload(dv))) {
+            delete fk;
+            return rc;
+        }
     }
     *out = fk;
     return TIK_OK;
@@ -431,6 +458,63 @@ int tik_fk_forward(tik_fk_t fk, const float* full_pose, const float* betas, cons
 
     if (!sparse) return lmk(0, B, st);
     return TIK_OK;
+}
+
+int tik_fk_joints(tik_fk_t fk, const float* full_pose, const float* betas, const float* expression,
+                  const float* transl, int B, const int* sel_host, int n_sel, float* out, void* stream) {
+    if (!fk || !full_pose || !out || B <= 0) return fail(TIK_E_INVALID, "tik_fk_joints: bad arguments");
+    if (sel_host && (n_sel < 1 || n_sel > tik::FKJ_MAX_SEL))
+        return fail(TIK_E_INVALID, "tik_fk_joints: n_sel must be 1..%d, got %d", tik::FKJ_MAX_SEL, n_sel);
+    hipStream_t st = (hipStream_t)stream;
+    tik::FkJointsArgs k{};   // the selection travels in the kernel arguments: nothing is uploaded per call
+    k.sel_all = sel_host ? 0 : 1;
+    k.n_out = sel_host ? n_sel : fk->njoints;
+    int npick = 0;           // vertex evaluations of this selection
+    for (int s = 0; s < k.n_out; ++s) {
+        const int j = sel_host ? sel_host[s] : s;
+        if (j < 0 || j >= fk->njoints) return fail(TIK_E_INVALID, "tik_fk_joints: joint index %d out of range [0, %d)", j, fk->njoints);
+        if (sel_host) k.sel[s] = (unsigned short)j;
+        npick += j < NJ ? 0 : j < NJ + fk->nextra ? 1 : 3;
+    }
+    if (fk->njoints > 65535) return fail(TIK_E_INVALID, "tik_fk_joints: too many joints");
+    // workspace: feat 512 + A_j 660 + chain joints 165 floats + the bin per body; never the mesh path's
+    // v_posed / vertex / ablk buffers or its second stream
+    int rc;
+    if ((rc = fk->jchain.reserve((size_t)B * NJ * 3)) || (fk->contour && (rc = fk->dyn_bin.reserve((size_t)B))) ||
+        (npick && ((rc = fk->feat.reserve((size_t)B * KP)) || (rc = fk->ajt.reserve((size_t)B * NJ * 12)))))
+        return rc;
+    tik::FkChainArgs c{};
+    c.B = B; c.nb = fk->nb; c.ne = fk->ne; c.kp = KP; c.kj = KJ; c.njoints = NJ; c.nchain = fk->nchain;
+    c.pose = full_pose; c.betas = betas; c.expr = expression; c.transl = transl; c.pose_mean = fk->pose_mean.p;
+    c.parents = fk->parents.p; c.chain = fk->chain.p; c.jt = fk->jt.p; c.jd = fk->jd.p;
+    c.feat = npick ? fk->feat.p : nullptr; c.ablk = nullptr; c.arows = 12;
+    c.ajt = npick ? fk->ajt.p : nullptr;
+    c.joints = fk->jchain.p; c.dyn_bin = fk->contour ? fk->dyn_bin.p : nullptr;
+    c.depth = fk->depth.p; c.maxdepth = fk->maxdepth;
+    Profiler* pf = fk->profiling ? &fk->prof : nullptr;
+    {
+        ProfRange pr(pf, "fk_chain", 0.0, 4.0 * (double)B * (NJ * 3 + 20 + NJ * 3 + (npick ? KP + 12 * NJ : 0)), st);
+        HIP_TRY(tik::launch_fk_chain(c, st));
+    }
+    k.B = B; k.nextra = fk->nextra; k.nlmk = fk->nlmk; k.ndyn = fk->ndyn;
+    k.nz = fk->dense ? 0 : fk->sp_nz;
+    k.feat = fk->feat.p; k.ajt = fk->ajt.p; k.jchain = fk->jchain.p; k.transl = transl;
+    k.PT = fk->PT.p; k.WT = fk->WT.p; k.nzw = reinterpret_cast<const int2*>(fk->nzw.p);
+    k.pick_v = fk->pick_v.p; k.pick_w = fk->pick_w.p; k.dyn_v = fk->dyn_v.p; k.dyn_w = fk->dyn_bary.p;
+    k.dyn_bin = fk->dyn_bin.p; k.out = out;
+    // algorithmic, per vertex evaluation: 3 dot products of 507 + the skinning sum + the 3x4 transform;
+    // bytes: feat and A_j in, the picked P^T rows once, the joints out
+    const double terms = k.nz ? k.nz : NJ;
+    ProfRange pr(pf, "fk_joints", 2.0 * B * npick * (3.0 * 507 + 12.0 * terms + 9.0),
+                 4.0 * ((double)B * (npick ? KP + 12 * NJ : 0) + 3.0 * 507 * npick + 3.0 * B * NJ + 3.0 * B * k.n_out), st);
+    HIP_TRY(tik::launch_fk_joints(k, st));
+    return TIK_OK;
+}
+
+long long tik_fk_workspace_bytes(tik_fk_t fk) {
+    if (!fk) return fail(TIK_E_INVALID, "null fk handle");
+    return (long long)(4 * (fk->feat.n + fk->ablk.n + fk->vposed.n + fk->verts_ws.n + fk->ajt.n + fk->zero_transl.n +
+                            fk->dyn_bin.n + fk->jchain.n) + 2 * fk->trash.n);
 }
 
 int tik_fk_profile(tik_fk_t fk, int max_launches) {

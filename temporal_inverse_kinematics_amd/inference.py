@@ -6,7 +6,7 @@ reference, each window's output frame 0 is the solution for frame idx
 
 CLI (README.md:24-26):
     python -m temporal_inverse_kinematics_amd.inference <moveai_3d.npz> [SMPLX_DIR]
-        [--ckpt model.ckpt] [--win-size 64] [--out poses.npy]
+        [--ckpt model.ckpt] [--win-size 64] [--out poses.npy] [--check]
 Without --ckpt the seeded synthetic weights are used (the trained checkpoint
 is not distributed with the reference: .MISSING_LARGE_BLOBS:2).
 """
@@ -54,9 +54,35 @@ def synthetic_model(win_size: int = 64, device="cuda", seed: int = 0, precision=
     return model.to(device).eval()
 
 
+def fk_check(poses, seq_3d_kps, smplx_model, betas=None) -> dict:
+    """How far the solved poses' FK lands from the keypoints they were solved
+    from: poses (F,66), seq_3d_kps (F,17,3) COCO. The FK COCO-17 joints (the
+    pose layout of run_test: hands zero, no translation; SMPLX.joints, no
+    mesh) and the keypoints are both made root-relative (mean of COCO 11/12,
+    the hips). -> {"per_joint": (F,17) distances on the host, "mpjpe": (F,),
+    "mean": float}."""
+    from .smplx_fk import split_pose156
+    dev = smplx_model.device
+    p = torch.as_tensor(np.ascontiguousarray(poses, dtype=np.float32), device=dev)
+    F = p.shape[0]
+    P = torch.zeros((F, 156), device=dev)
+    P[:, :66] = p[:, :66]
+    b = None
+    if betas is not None:
+        b = torch.as_tensor(np.asarray(betas, np.float32)[:smplx_model.num_betas][None], device=dev).expand(F, -1).contiguous()
+    with torch.no_grad():
+        fk = smplx_model.joints(split_pose156(P), b, None, None, select="coco")
+    kps = torch.as_tensor(np.ascontiguousarray(seq_3d_kps, dtype=np.float32), device=dev).reshape(F, 17, 3)
+    rel = lambda x: x - 0.5 * (x[:, 11:12] + x[:, 12:13])
+    per_joint = (rel(fk) - rel(kps)).norm(dim=2).cpu().numpy()
+    mpjpe = per_joint.mean(axis=1)
+    return {"per_joint": per_joint, "mpjpe": mpjpe, "mean": float(mpjpe.mean())}
+
+
 def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = None, win_size: int = 64,
-             device="cuda"):
-    """inference.run_test:110-145: moveai npz -> COCO -> IK -> (optional) SMPL-X FK."""
+             device="cuda", check: bool = False):
+    """inference.run_test:110-145: moveai npz -> COCO -> IK -> (optional) SMPL-X FK.
+    check=True (with an SMPL-X dir): the result gains "fk_check" (fk_check above)."""
     d = np.load(npz_path, allow_pickle=False)
     # the moveai_3d -> COCO conversion on the device (one gather kernel, bit-identical to the host form)
     seq = kp.moveai3d_to_coco_device(torch.as_tensor(np.ascontiguousarray(d["joints_3d"], dtype=np.float32),
@@ -76,6 +102,8 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
         joints, verts = run_smpl_inference({"poses": sample, "gender": "male"}, models, device,
                                            apply_trans=False, apply_shape=False, return_mesh=True)
         result.update(joints=joints, vertices=verts)
+        if check:
+            result["fk_check"] = fk_check(poses, result["coco"], models["male"])
     return result
 
 
@@ -86,11 +114,15 @@ def main(argv=None):
     p.add_argument("--ckpt")
     p.add_argument("--win-size", type=int, default=64)
     p.add_argument("--out")
+    p.add_argument("--check", action="store_true",
+                   help="with SMPLX_DIR: compare the FK joints of the solved poses with the input keypoints")
     a = p.parse_args(argv)
-    r = run_test(a.npz, a.smplx_dir, a.ckpt, a.win_size)
+    r = run_test(a.npz, a.smplx_dir, a.ckpt, a.win_size, check=a.check)
     if a.out:
         np.save(a.out, r["poses"])
     print(f"solved {r['poses'].shape[0]} frames -> poses {r['poses'].shape}")
+    if "fk_check" in r:
+        print(f"FK check: mean root-relative joint distance {r['fk_check']['mean']:.6f}")
     return 0
 
 

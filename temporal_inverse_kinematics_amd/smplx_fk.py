@@ -79,6 +79,43 @@ def constants_from_npz(path: str, num_betas: int = NUM_BETAS, num_expr: int = NU
     return c
 
 
+MAX_SELECT = 256   # entries of a joint selection (include/tik.h, tik_fk_joints)
+
+
+def resolve_select(select, num_joints: int):
+    """A joint selection -> list of SMPL-X joint indices, or None for all joints.
+    `select`: None, "coco" (the COCO-17 order, training_data.SMPLX_TO_COCO) or a
+    sequence of ints in [0, num_joints), at most MAX_SELECT of them, duplicates
+    allowed. ValueError otherwise; the library is not touched."""
+    if select is None:
+        return None
+    if isinstance(select, str):
+        if select != "coco":
+            raise ValueError(f"unknown joint selection {select!r}; expected 'coco' or a sequence of indices")
+        from .training_data import SMPLX_TO_COCO
+        select = SMPLX_TO_COCO
+    sel = [int(j) for j in select]
+    if not 1 <= len(sel) <= MAX_SELECT:
+        raise ValueError(f"a joint selection has 1..{MAX_SELECT} entries, got {len(sel)}")
+    for j in sel:
+        if not 0 <= j < num_joints:
+            raise ValueError(f"joint index {j} out of range [0, {num_joints})")
+    return sel
+
+
+def split_pose156(P: torch.Tensor, apply_root_rot: bool = True) -> torch.Tensor:
+    """AMASS pose rows (R,156) [root 3 | body 63 | lhand 45 | rhand 45] on the
+    device -> full_pose (R,55,3) (jaw and eyes zero), smpl_util.py:58-66."""
+    R = P.shape[0]
+    full = torch.zeros((R, 55, 3), device=P.device)
+    if apply_root_rot:
+        full[:, 0] = P[:, :3]
+    full[:, 1:22] = P[:, 3:66].reshape(R, 21, 3)
+    full[:, 25:40] = P[:, 66:111].reshape(R, 15, 3)
+    full[:, 40:55] = P[:, 111:156].reshape(R, 15, 3)
+    return full
+
+
 class SMPLX:
     """The smplx.SMPLX object the reference drives (pose2rot, use_pca=False)."""
 
@@ -148,6 +185,37 @@ class SMPLX:
                                               _lib.stream_of(fp)), "SMPLX.forward")
         return joints, verts
 
+    def joints(self, full_pose: torch.Tensor, betas=None, expression=None, transl=None, select=None, out=None):
+        """full_pose (B,55,3) device -> joints (B,n,3) without building the mesh
+        (tik_fk_joints): only the vertices the selected joints are made of are
+        evaluated, in fp32 FMAs for either `precision`. select: None (all
+        num_joints), "coco" (COCO-17 order) or a sequence of joint indices (at
+        most 256, duplicates allowed), the output columns in that order. Joints
+        below 55 are bit for bit full_forward's, the others within 2e-4 of them.
+        out: optional preallocated contiguous float32 (B,n,3) tensor."""
+        fp = full_pose.reshape(-1, 55, 3).contiguous()
+        B = fp.shape[0]
+        args = [t.contiguous() if t is not None else None for t in (betas, expression, transl)]
+        _lib.require_gpu(fp, *args)
+        sel = resolve_select(select, self.num_joints)
+        n = self.num_joints if sel is None else len(sel)
+        if out is not None:
+            if out.shape != (B, n, 3) or not out.is_contiguous() or out.dtype != torch.float32:
+                raise ValueError(f"out must be a contiguous float32 (B, {n}, 3) tensor")
+            _lib.require_gpu(out)
+        else:
+            out = torch.empty((B, n, 3), device=fp.device, dtype=torch.float32)
+        csel = None if sel is None else (_lib.ctypes.c_int * n)(*sel)
+        _lib.check(_lib.load().tik_fk_joints(self._h, fp.data_ptr(), _lib.ptr(args[0]), _lib.ptr(args[1]),
+                                             _lib.ptr(args[2]), B, csel, n, out.data_ptr(), _lib.stream_of(fp)),
+                   "SMPLX.joints")
+        return out
+
+    @property
+    def workspace_bytes(self) -> int:
+        """Device workspace the handle owns right now (tik_fk_workspace_bytes)."""
+        return int(_lib.check(_lib.load().tik_fk_workspace_bytes(self._h)))
+
     def __call__(self, global_orient=None, body_pose=None, betas=None, left_hand_pose=None, right_hand_pose=None,
                  transl=None, expression=None, jaw_pose=None, leye_pose=None, reye_pose=None, return_verts=True):
         ref = next(t for t in (body_pose, global_orient, left_hand_pose, right_hand_pose, betas) if t is not None)
@@ -175,6 +243,27 @@ def load_smplx_models(smplx_dir, device, batch_size):
     return out
 
 
+def _smpl_inputs(data, model, device, R, apply_trans, apply_root_rot, apply_shape):
+    """The device inputs of run_smpl_inference / run_smpl_joints: R rows, the first F from `data`."""
+    poses = np.asarray(data["poses"], dtype=np.float32)
+    F = poses.shape[0]
+    if poses.shape[1] < 156:
+        poses = np.concatenate([poses, np.zeros((F, 156 - poses.shape[1]), np.float32)], 1)
+    P = torch.zeros((R, 156), device=device)
+    P[:F] = torch.from_numpy(np.ascontiguousarray(poses[:, :156])).to(device)
+    full = split_pose156(P, apply_root_rot)
+    trans = None
+    if apply_trans:
+        trans = torch.zeros((R, 3), device=device)
+        trans[:F] = torch.from_numpy(np.asarray(data["trans"], np.float32)).to(device)
+    betas = None
+    if apply_shape:
+        b = np.asarray(data["betas"], np.float32)[:model.num_betas][None]
+        betas = torch.zeros((R, b.shape[1]), device=device)
+        betas[:F] = torch.from_numpy(np.tile(b, (F, 1))).to(device)
+    return full, betas, trans
+
+
 def run_smpl_inference(data, smplx_models, device, apply_trans=True, apply_root_rot=True, apply_shape=True,
                        return_mesh=False):
     """smpl_util.py:22-82: poses (F,>=66) [+ trans, betas] -> joints (F,144,3) [, verts].
@@ -188,32 +277,25 @@ def run_smpl_inference(data, smplx_models, device, apply_trans=True, apply_root_
     those rows are solved from zero inputs too. Pinned by
     tests/test_smpl_orchestration.py against the reference's own function."""
     model = smplx_models[str(data["gender"])]
-    poses = np.asarray(data["poses"], dtype=np.float32)
-    F = poses.shape[0]
+    F = np.asarray(data["poses"]).shape[0]
     bs = max(1, int(getattr(model, "batch_size", 1) or 1))
     R = F + ((-F) % bs if return_mesh else 0)   # rows solved: + the reference's mesh padding
-    if poses.shape[1] < 156:
-        poses = np.concatenate([poses, np.zeros((F, 156 - poses.shape[1]), np.float32)], 1)
-    P = torch.zeros((R, 156), device=device)
-    P[:F] = torch.from_numpy(np.ascontiguousarray(poses[:, :156])).to(device)
-    full = torch.zeros((R, 55, 3), device=device)
-    if apply_root_rot:
-        full[:, 0] = P[:, :3]
-    full[:, 1:22] = P[:, 3:66].reshape(R, 21, 3)
-    full[:, 25:40] = P[:, 66:111].reshape(R, 15, 3)
-    full[:, 40:55] = P[:, 111:156].reshape(R, 15, 3)
-    trans = None
-    if apply_trans:
-        trans = torch.zeros((R, 3), device=device)
-        trans[:F] = torch.from_numpy(np.asarray(data["trans"], np.float32)).to(device)
-    betas = None
-    if apply_shape:
-        b = np.asarray(data["betas"], np.float32)[:model.num_betas][None]
-        betas = torch.zeros((R, b.shape[1]), device=device)
-        betas[:F] = torch.from_numpy(np.tile(b, (F, 1))).to(device)
+    full, betas, trans = _smpl_inputs(data, model, device, R, apply_trans, apply_root_rot, apply_shape)
     with torch.no_grad():
         joints, verts = model.full_forward(full, betas, None, trans, return_verts=return_mesh)
     j = joints[:F].cpu().numpy()
     if return_mesh:
         return j, verts.cpu().numpy()
     return j
+
+
+def run_smpl_joints(data, smplx_models, device, apply_trans=True, apply_root_rot=True, apply_shape=True,
+                    select=None):
+    """run_smpl_inference(..., return_mesh=False) on the mesh-free path
+    (SMPLX.joints): joints (F,n,3) on the host, n = 144 or len(select)
+    (select: None, "coco" or joint indices, the columns in that order)."""
+    model = smplx_models[str(data["gender"])]
+    F = np.asarray(data["poses"]).shape[0]
+    full, betas, trans = _smpl_inputs(data, model, device, F, apply_trans, apply_root_rot, apply_shape)
+    with torch.no_grad():
+        return model.joints(full, betas, None, trans, select=select).cpu().numpy()

@@ -62,20 +62,20 @@ def rotate_root_z(poses: torch.Tensor, angle: float) -> torch.Tensor:
     return poses
 
 
-def fk_joints(model, poses: torch.Tensor, betas: np.ndarray, apply_root_rot: bool = True) -> torch.Tensor:
-    """smpl_util.py:22-82 with apply_trans=False, on device rows: (F, >=66) -> joints (F, J, 3)."""
+def fk_joints(model, poses: torch.Tensor, betas: np.ndarray, apply_root_rot: bool = True, select=None) -> torch.Tensor:
+    """smpl_util.py:22-82 with apply_trans=False, on device rows: (F, >=66) -> joints (F, J, 3).
+    select (None | "coco" | joint indices): only those joints, (F, n, 3) in that
+    order, on the mesh-free path (SMPLX.joints); the default builds the body."""
+    from .smplx_fk import split_pose156
     F = poses.shape[0]
     P = torch.zeros((F, 156), device=poses.device, dtype=torch.float32)
     w = min(156, poses.shape[1])
     P[:, :w] = poses[:, :w]
-    full = torch.zeros((F, 55, 3), device=poses.device)
-    if apply_root_rot:
-        full[:, 0] = P[:, :3]
-    full[:, 1:22] = P[:, 3:66].reshape(F, 21, 3)
-    full[:, 25:40] = P[:, 66:111].reshape(F, 15, 3)
-    full[:, 40:55] = P[:, 111:156].reshape(F, 15, 3)
+    full = split_pose156(P, apply_root_rot)
     b = torch.from_numpy(np.asarray(betas, np.float32)[:model.num_betas][None]).to(poses.device)
     with torch.no_grad():
+        if select is not None:
+            return model.joints(full, b.expand(F, -1).contiguous(), None, None, select=select)
         joints, _ = model.full_forward(full, b.expand(F, -1).contiguous(), None, None, return_verts=False)
     return joints
 
@@ -83,11 +83,17 @@ def fk_joints(model, poses: torch.Tensor, betas: np.ndarray, apply_root_rot: boo
 class AmassDataset(torch.utils.data.Dataset):
     """data_amass.py:87-218. `amass_paths`: AMASS npz files or dicts with
     poses (F, >=66), betas, gender. Items are numpy dicts like the reference;
-    `get_batch(indices)` returns device tensors for a whole batch."""
+    `get_batch(indices)` returns device tensors for a whole batch.
+
+    mesh_free=True: the per-epoch FK takes only the target keypoints' joints,
+    without building the bodies (SMPLX.joints). Each sequence's `keypoints_3d`
+    is then (F, 17, 3), already in target (COCO) order, instead of the (F, 144,
+    3) SMPL-X joints; items agree with the default's within the two FK paths'
+    difference (a few 1e-4 at most)."""
 
     def __init__(self, smplx_models, amass_paths: List, window_size: int, keypoint_format: str, device="cuda",
                  add_gaussian_noise=True, shape_db_path: Optional[Path] = None, aug_shape=True,
-                 aug_root_orientation=True, noise_seed: int = 0):
+                 aug_root_orientation=True, noise_seed: int = 0, mesh_free: bool = False):
         self.origin_amass_paths = amass_paths
         self.device = torch.device(device)
         self.smplx_models = smplx_models
@@ -98,6 +104,7 @@ class AmassDataset(torch.utils.data.Dataset):
         self.aug_root_orientation = aug_root_orientation
         self.aug_shape = aug_shape
         self.noise_seed = int(noise_seed)
+        self.mesh_free = bool(mesh_free)
         self.epoch = 0
         self.smplx_shape_db = None
         if shape_db_path is not None:
@@ -144,7 +151,8 @@ class AmassDataset(torch.utils.data.Dataset):
             data["betas"] = np.asarray(data["betas"], np.float32)
             model = self.smplx_models[str(data["gender"])]
             data["poses"] = poses
-            data["keypoints_3d"] = fk_joints(model, poses, data["betas"], apply_root_rot=True)
+            data["keypoints_3d"] = fk_joints(model, poses, data["betas"], apply_root_rot=True,
+                                             select=self.target_kps_mapping if self.mesh_free else None)
             data_s.append(data)
         return data_s
 
@@ -221,7 +229,8 @@ class AmassDataset(torch.utils.data.Dataset):
         tgt = torch.empty((B, 1, 66), device=self.device, dtype=torch.float32)
         if B:
             meta = torch.from_numpy(np.stack([self._starts[seq], F, local, idx, seq]).astype(np.int32)).to(self.device)
-            cmap = (ctypes.c_int * 17)(*self.target_kps_mapping)
+            # mesh_free: the stored joints are the 17 targets already, in order
+            cmap = (ctypes.c_int * 17)(*(range(17) if self.mesh_free else self.target_kps_mapping))
             sig = (ctypes.c_float * 17)(*[float(s) for s in self.kps_noise_sigmas])
             seed = self.noise_key
             _lib.check(_lib.load().tik_train_windows(

@@ -1,0 +1,410 @@
+"""The mesh-free joints path (tik_fk_joints, SMPLX.joints, run_smpl_joints,
+AmassDataset(mesh_free=True), inference.fk_check) against the numpy SMPL-X
+oracle (oracle/smplx_lbs.py) at the FK tolerance of tests/test_gpu_fk.py, and
+bit for bit against itself across batch sizes, positions and selections.
+
+The kernel's body tile is TILE = 64 bodies (one lane per body, fk.h FKJ_TB):
+the batches below include 63, 64 and 65. Launches of at most 64 workgroups
+(body tiles x groups of 8 columns) take the split mapping (a workgroup per
+column, its waves over k): for all 144 joints that is B <= SPLIT_MAX = 192.
+"""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import fk_joints_edges as fje
+import memedge as me
+from oracle import amass as oa
+from oracle import smplx_lbs as sl
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-4          # tests/test_gpu_fk.py
+TILE = 64
+SPLIT_MAX = 192     # all joints: 3 tiles x 18 column groups = 54 workgroups; 193 bodies make 72
+HERE = os.path.dirname(os.path.abspath(__file__))
+_ORACLE = {}
+
+
+def cu(a):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def oracle_bins(c, pose):
+    """The contour bin of each body, from the oracle's own functions (smplx_forward keeps it to itself)."""
+    p = np.asarray(pose, np.float64).reshape(-1, 55, 3) + c["pose_mean"].astype(np.float64).reshape(1, 55, 3)
+    R = sl.batch_rodrigues(p.reshape(-1, 3)).reshape(-1, 55, 3, 3)
+    rel = np.broadcast_to(np.eye(3), (R.shape[0], 3, 3)).copy()
+    for j in sl.neck_kin_chain(c["parents"].astype(np.int64)):
+        rel = R[:, j] @ rel
+    y = np.round(np.minimum(-sl.rot_mat_to_euler(rel) * 180.0 / np.pi, 39)).astype(np.int64)
+    return np.where(y < 0, np.where(y < -39, 78, 39 - y), y)
+
+
+def oracle_joints(B, bare=False):
+    """smplx_forward(return_verts=False) on fk_inputs(B), computed once per (B, bare) and left unchanged."""
+    if (B, bare) not in _ORACLE:
+        pose, betas, expr, transl = me.fk_inputs(B)
+        j = sl.smplx_forward(me.fk_consts(), pose, return_verts=False) if bare else \
+            sl.smplx_forward(me.fk_consts(), pose, betas, expr, transl, return_verts=False)
+        j.setflags(write=False)
+        _ORACLE[(B, bare)] = j
+    return _ORACLE[(B, bare)]
+
+
+@pytest.fixture(scope="module")
+def consts():
+    me.lib()
+    return me.fk_consts()
+
+
+@pytest.fixture(scope="module", params=["bf16x3", "fp32"])
+def model(consts, request):
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    return SMPLX(consts, batch_size=9, precision=request.param)
+
+
+@pytest.fixture(scope="module")
+def model1(consts):
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    return SMPLX(consts, batch_size=9)
+
+
+@pytest.fixture(scope="module")
+def all37(model1):
+    """joints(select=None) of fk_inputs(37): the reference of the selection and batch tests."""
+    return model1.joints(*[cu(a) for a in me.fk_inputs(37)])
+
+
+# ---------------------------------------------------------------- 1. oracle parity
+def test_inputs_cover_the_contour_edge_bins(consts):
+    b37, b3 = oracle_bins(consts, me.fk_inputs(37)[0]), oracle_bins(consts, me.fk_inputs(3)[0])
+    for bins in (b37, np.concatenate([b37, b3])):
+        assert (bins >= 40).any() and (bins == 39).any() and (bins == 78).any(), sorted(set(bins.tolist()))
+    assert len(set(b37.tolist())) >= 10
+
+
+@pytest.mark.parametrize("bare", [False, True], ids=["shape_expr_transl", "pose_only"])
+@pytest.mark.parametrize("B", [1, 3, 37, TILE - 1, TILE, TILE + 1])
+def test_joints_vs_oracle(consts, model, B, bare):
+    pose, betas, expr, transl = me.fk_inputs(B)
+    if B in (3, 37):   # a condition of the case, not a hope: the clamp, the last bin and the negative bins are in
+        bins = oracle_bins(consts, pose)
+        assert (bins == 39).any() and (bins == 78).any() and (bins >= 40).any()
+    j = model.joints(cu(pose)) if bare else model.joints(cu(pose), cu(betas), cu(expr), cu(transl))
+    assert j.shape == (B, 144, 3)
+    err = np.abs(j.cpu().numpy() - oracle_joints(B, bare)).max()
+    print(f"B={B} bare={bare} {model.precision}: max |joints - oracle| = {err:.3e}")
+    assert err < TOL
+
+
+# ---------------------------------------------------------------- 2, 3. against full_forward
+def test_chain_joints_bitwise_and_cross_path(model):
+    args = [cu(a) for a in me.fk_inputs(37)]
+    j = model.joints(*args)
+    jf, _ = model.full_forward(*args, return_verts=False)
+    assert torch.equal(j[:, :55], jf[:, :55])
+    d = float((j[:, 55:] - jf[:, 55:]).abs().max())
+    print(f"{model.precision}: max |joints - full_forward| over joints 55.. = {d:.3e}")
+    assert d < 2 * TOL   # both within TOL of the oracle
+
+
+# ---------------------------------------------------------------- 4. selection
+SELECTIONS = {
+    "coco": "coco",
+    "chain_only": [0, 54, 12, 7],
+    "dups_reversed": [143, 143, 127, 126, 100, 76, 75, 55, 54, 3, 3, 0],
+    "full_256": [(7 * i) % 144 for i in range(256)],
+}
+
+
+@pytest.mark.parametrize("name", list(SELECTIONS))
+def test_selection_columns_bitwise(model1, all37, name):
+    from temporal_inverse_kinematics_amd.training_data import SMPLX_TO_COCO
+    sel = SELECTIONS[name]
+    idx = SMPLX_TO_COCO if sel == "coco" else sel
+    got = model1.joints(*[cu(a) for a in me.fk_inputs(37)], select=sel)
+    assert got.shape == (37, len(idx), 3)
+    assert torch.equal(got, all37[:, idx])
+
+
+@pytest.mark.parametrize("sel", [list(range(144)) + list(range(113)), [-1], [144], [0, 5, 144], []])
+def test_selection_rejected(model1, sel):
+    with pytest.raises(ValueError):
+        model1.joints(cu(me.fk_inputs(3)[0]), select=sel)
+
+
+def test_c_abi_rejects_bad_arguments(model1):
+    from temporal_inverse_kinematics_amd import _lib
+    L = _lib.load()
+    pose = cu(me.fk_inputs(3)[0])
+    out = torch.empty((3, 257, 3), device="cuda")
+    call = lambda sel, n, B=3, p=pose.data_ptr(), o=out.data_ptr(): L.tik_fk_joints(
+        model1._h, p, 0, 0, 0, B, None if sel is None else (_lib.ctypes.c_int * len(sel))(*sel), n, o, 0)
+    assert call([0] * 257, 257) == _lib.TIK_E_INVALID
+    assert call([0], 0) == _lib.TIK_E_INVALID
+    assert call([144], 1) == _lib.TIK_E_INVALID
+    assert call([-1], 1) == _lib.TIK_E_INVALID
+    assert call(None, 0, B=0) == _lib.TIK_E_INVALID
+    assert call(None, 0, p=0) == _lib.TIK_E_INVALID
+    assert call(None, 0, o=0) == _lib.TIK_E_INVALID
+    assert call(None, 0) == _lib.TIK_OK   # NULL selection: n_sel ignored
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------- 5. batch invariance
+def test_batch_invariance(consts, model1, all37):
+    a37 = [cu(a) for a in me.fk_inputs(37)]
+    assert torch.equal(model1.joints(*[a[36:37] for a in a37]), all37[36:37])
+    inp = me.fk_inputs(4096)
+    a = [cu(x) for x in inp]
+    big = model1.joints(*a)
+    assert torch.isfinite(big).all()
+    assert torch.equal(model1.joints(*[x[4095:4096] for x in a]), big[4095:4096])
+    pick = [0, 2047, 4095]
+    jr = sl.smplx_forward(consts, *[x[pick] for x in inp], return_verts=False)
+    assert np.abs(big[pick].cpu().numpy() - jr).max() < TOL
+    for name in ("coco", "full_256"):   # selections on the lane-per-body mapping (64 tiles)
+        from temporal_inverse_kinematics_amd.training_data import SMPLX_TO_COCO
+        sel = SELECTIONS[name]
+        assert torch.equal(model1.joints(*a, select=sel), big[:, SMPLX_TO_COCO if sel == "coco" else sel]), name
+
+
+def test_both_mappings_same_bits(consts, model1):
+    """One body past the split mapping's last batch: the lane-per-body mapping on four tiles (the last
+    holds one body) gives the bits of the split mapping, for all joints and for a selection."""
+    B = SPLIT_MAX + 1
+    inp = me.fk_inputs(B)
+    a = [cu(x) for x in inp]
+    wide = model1.joints(*a)
+    assert torch.equal(model1.joints(*[x[:SPLIT_MAX] for x in a]), wide[:SPLIT_MAX])
+    assert torch.equal(model1.joints(*[x[SPLIT_MAX:] for x in a]), wide[SPLIT_MAX:])
+    pick = [0, 100, SPLIT_MAX]
+    jr = sl.smplx_forward(consts, *[x[pick] for x in inp], return_verts=False)
+    assert np.abs(wide[pick].cpu().numpy() - jr).max() < TOL
+    sel = SELECTIONS["dups_reversed"]
+    assert torch.equal(model1.joints(*a, select=sel), wide[:, sel])   # 4 x 2 workgroups: split
+
+
+# ---------------------------------------------------------------- 6. weight layouts
+def _weights(consts, nzmax):
+    """The construction of tests/test_gpu_fk.py::test_fk_sparse_skinning."""
+    c = dict(consts)
+    rng = np.random.default_rng(nzmax)
+    V = c["v_template"].shape[0]
+    w = np.zeros((V, 55))
+    for v in range(V):
+        k = rng.integers(1, nzmax + 1)
+        w[v, rng.choice(55, size=k, replace=False)] = rng.uniform(0.05, 1.0, k)
+    w /= w.sum(axis=1, keepdims=True)
+    w[w == 0] = 1e-13   # below the threshold: dropped where the pairs are used
+    c["lbs_weights"] = w.astype(np.float32)
+    return c
+
+
+@pytest.mark.parametrize("nzmax,skin", [(4, "sparse"), (12, "sparse"), (20, "sparse"), (12, "dense")])
+def test_weight_layouts(consts, nzmax, skin):
+    """4 and 16 pairs per vertex, more than 16 live joints (no pairs: the dense WT rows), and TIK_FK_SKIN=dense."""
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    c = _weights(consts, nzmax)
+    inp = me.fk_inputs(37)
+    with me.env(TIK_FK_SKIN=skin):
+        m = SMPLX(c, batch_size=9)
+    j = m.joints(*[cu(a) for a in inp])
+    jr = sl.smplx_forward(c, *inp, return_verts=False)
+    assert np.abs(j.cpu().numpy() - jr).max() < TOL
+
+
+# ---------------------------------------------------------------- 7. duplicate and degenerate picks
+def test_duplicate_and_degenerate_picks(consts):
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    inp = me.fk_inputs(37)
+    c = {k: np.array(v, copy=True) for k, v in consts.items()}
+    c["extra_verts"][1] = c["extra_verts"][0]
+    bins = oracle_bins(c, inp[0])
+    f_static = int(c["lmk_faces_idx"][0])
+    f_dyn = int(c["dynamic_lmk_faces_idx"][39, 0])   # bin 39: the clamp, hit by these inputs
+    assert (bins == 39).any() and f_dyn != f_static
+    for f in (f_static, f_dyn):
+        v, _, w = c["faces"][f]
+        c["faces"][f] = (v, v, w)
+    j = SMPLX(c, batch_size=9).joints(*[cu(a) for a in inp])
+    jr = sl.smplx_forward(c, *inp, return_verts=False)
+    assert np.abs(j.cpu().numpy() - jr).max() < TOL
+    assert torch.equal(j[:, 55], j[:, 56])
+
+
+# ---------------------------------------------------------------- 8. workspace
+def test_workspace_stays_small(consts, model1):
+    """feat 512 + A_j 660 + chain joints 165 floats + the bin: 5352 B per body; the cap is about twice that.
+    The mesh path's vertex workspace alone is 125,700 B per body."""
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    B = 4096
+    small = [cu(a) for a in me.fk_inputs(37)]
+    want = model1.full_forward(*small)
+    m = SMPLX(consts, batch_size=9)
+    assert m.workspace_bytes == 0
+    m.joints(*[cu(a) for a in me.fk_inputs(B)])
+    torch.cuda.synchronize()
+    ws = m.workspace_bytes
+    print(f"workspace after joints at B={B}: {ws} B = {ws / B:.0f} B per body")
+    assert 0 < ws < B * 16 * 1024
+    got = m.full_forward(*small)
+    me.assert_same({"j": got[0], "v": got[1]}, {"j": want[0], "v": want[1]}, "full_forward after joints")
+    m.joints(*small, select="coco")
+    again = m.full_forward(*small)
+    me.assert_same({"j": again[0], "v": again[1]}, {"j": want[0], "v": want[1]}, "full_forward, joints, full_forward")
+
+
+# ---------------------------------------------------------------- 9. memory edges
+@pytest.fixture(scope="module")
+def edge_ref():
+    me.lib()
+    return {c: fje.joints_family(c, reserve=None) for c in fje.CONFIGS}
+
+
+@pytest.mark.parametrize("reserve", [fje.RESERVE, None], ids=["oversize", "exact"])
+@pytest.mark.parametrize("fill", ["ff", "7f"])
+@pytest.mark.parametrize("config", fje.CONFIGS)
+def test_joints_poisoned_workspace(edge_ref, config, fill, reserve):
+    with me.poison(fill):
+        got = fje.joints_family(config, reserve=reserve)
+    me.assert_same(got, edge_ref[config], ("fk_joints", config, fill, reserve))
+
+
+@pytest.mark.parametrize("B", fje.BATCHES)
+def test_joints_sentinel_slabs(model1, B):
+    from test_gpu_memory_edges import _sentinel
+    inp = [cu(a) for a in me.fk_inputs(B)]
+    for sel in fje.SELECTS:
+        n = 144 if sel is None else 17 if sel == "coco" else len(sel)
+
+        def call(p):
+            a = [p.inp(t, w) for t, w in zip(inp, ("pose", "betas", "expr", "transl"))]
+            return {"joints": model1.joints(*a, select=sel, out=p.out((B, n, 3)))}
+        _sentinel(call, ("fk_joints", B, str(sel)))
+
+
+def test_joints_no_guard_zone_written():
+    import fk_joints_guard_child as child
+    me.lib()
+    env = dict(os.environ)
+    env.pop("TIK_POISON", None)
+    env["TIK_GUARD"] = "1"
+    p = subprocess.run([sys.executable, os.path.join(HERE, "fk_joints_guard_child.py")], env=env, capture_output=True,
+                       text=True, timeout=300)
+    lines = {d["family"]: d for d in (json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{"))}
+    assert p.returncode == 0, (p.returncode, lines, p.stderr[-3000:])
+    assert sorted(lines) == sorted(child.FAMILY_NAMES)
+    for name, r in lines.items():
+        assert r["checks"] > 0 and r["bad"] == 0, (name, r)
+
+
+# ---------------------------------------------------------------- 10. run_smpl_joints
+def test_run_smpl_joints_vs_run_smpl_inference(consts):
+    """The data of tests/test_gpu_fk.py::test_run_smpl_inference_api."""
+    from temporal_inverse_kinematics_amd.smplx_fk import load_smplx_models, run_smpl_inference, run_smpl_joints
+    from temporal_inverse_kinematics_amd.training_data import SMPLX_TO_COCO
+    models = load_smplx_models(None, "cuda", 9)
+    rng = np.random.default_rng(0)
+    F = 20
+    poses = rng.normal(0, 0.3, (F, 156)).astype(np.float32)
+    data = {"poses": poses, "gender": "male", "trans": rng.normal(0, 1, (F, 3)), "betas": rng.normal(0, 1, 16)}
+    for kw in ({}, {"apply_trans": False, "apply_shape": False}, {"apply_root_rot": False}):
+        want = run_smpl_inference(data, models, "cuda", return_mesh=False, **kw)
+        got = run_smpl_joints(data, models, "cuda", **kw)
+        assert got.shape == want.shape == (F, 144, 3)
+        assert np.array_equal(got[:, :55], want[:, :55])
+        assert np.abs(got[:, 55:] - want[:, 55:]).max() < 2 * TOL
+        coco = run_smpl_joints(data, models, "cuda", select="coco", **kw)
+        assert np.array_equal(coco, got[:, SMPLX_TO_COCO])
+
+
+# ---------------------------------------------------------------- 11. AmassDataset(mesh_free=True)
+def _sequences(lens, seed=0):
+    """As tests/test_gpu_train_data.py."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i, F in enumerate(lens):
+        t = np.linspace(0, 2 * np.pi, F, dtype=np.float32)[:, None]
+        base = rng.normal(0, 0.3, (1, 156)).astype(np.float32)
+        amp = rng.normal(0, 0.2, (1, 156)).astype(np.float32)
+        out.append({"poses": (base + amp * np.sin(t + i)).astype(np.float32),
+                    "betas": rng.normal(0, 1, 10).astype(np.float32), "gender": ["male", "female", "neutral"][i % 3]})
+    return out
+
+
+def test_amass_dataset_mesh_free():
+    from temporal_inverse_kinematics_amd.smplx_fk import load_smplx_models
+    from temporal_inverse_kinematics_amd.training_data import AmassDataset, SMPLX_TO_COCO
+    me.lib()
+    lens = [80, 131, 65, 200]
+    seqs = _sequences(lens)
+    free_models = load_smplx_models(None, "cuda", batch_size=9)
+    idx = np.array([0, 1, 31, 32, 33, 48, 79, 80, 100, 210, 211, 240, 275, 276, 300, sum(lens) - 1])
+    off = np.concatenate([[0], np.cumsum(lens)])
+    # noise off: against the default dataset
+    df = AmassDataset(free_models, seqs, 64, "coco", add_gaussian_noise=False, mesh_free=True)
+    for g, m in free_models.items():
+        assert m.workspace_bytes < sum(lens) * 16 * 1024, g
+    dd = AmassDataset(load_smplx_models(None, "cuda", batch_size=9), seqs, 64, "coco", add_gaussian_noise=False)
+    assert [tuple(d["keypoints_3d"].shape) for d in df.data_anims] == [(n, 17, 3) for n in lens]
+    bf, bd = df.get_batch(idx), dd.get_batch(idx)
+    assert torch.equal(bf["poses"], bd["poses"]) and torch.equal(bf["betas"], bd["betas"])
+    d = float((bf["keypoints_3d"] - bd["keypoints_3d"]).abs().max())
+    print(f"mesh_free vs default windows: max |diff| = {d:.3e}")
+    assert d < 4 * TOL   # two paths within 2 TOL of each other, doubled by the root-relative subtraction
+    # noise on: every item against the oracle's __getitem__ on the mesh-free joints at their SMPL-X slots
+    dn = AmassDataset(free_models, seqs, 64, "coco", add_gaussian_noise=True, noise_seed=7, mesh_free=True)
+    b = dn.get_batch(idx)
+    kp, ps = b["keypoints_3d"].cpu().numpy(), b["poses"].cpu().numpy()
+    for r, i in enumerate(idx):
+        s = int(np.searchsorted(off, i, side="right") - 1)
+        a = dn.data_anims[s]
+        full = np.zeros((lens[s], 144, 3), np.float32)
+        full[:, SMPLX_TO_COCO] = a["keypoints_3d"].cpu().numpy()
+        ref = oa.getitem(full, a["poses"].cpu().numpy(), a["betas"], int(i - off[s]), 32, int(i), add_noise=True,
+                         seed=dn.noise_key)
+        assert np.abs(kp[r] - ref["keypoints_3d"]).max() < 2e-6, i
+        assert np.array_equal(ps[r], ref["poses"]), i
+    assert torch.equal(dn.get_batch(idx[::-1])["keypoints_3d"], b["keypoints_3d"].flip(0))
+    assert torch.equal(dn.get_batch(idx[3:9])["keypoints_3d"], b["keypoints_3d"][3:9])
+    assert np.array_equal(dn[int(idx[5])]["keypoints_3d"], kp[5])
+
+
+# ---------------------------------------------------------------- 12. fk_check
+def test_fk_check_and_run_test(tmp_path):
+    from conftest import golden
+    from temporal_inverse_kinematics_amd import synthetic as syn
+    from temporal_inverse_kinematics_amd.inference import fk_check, run_test
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    from temporal_inverse_kinematics_amd.training_data import SMPLX_TO_COCO
+    me.lib()
+    seq = syn.load_sample_coco()
+    assert seq.shape == (231, 17, 3)
+    k = golden("keypoints.npz")
+    src = tmp_path / "cam01_track00.npz"
+    np.savez(src, joints_3d=k["moveai_joints"].astype(np.float32), joint_3d_names=k["moveai_names"])
+    plain = run_test(str(src), "synthetic", win_size=64)       # the shipped sample through synthetic_model(64)
+    assert sorted(plain) == ["coco", "joints", "poses", "vertices"]
+    assert np.array_equal(plain["coco"], seq.astype(np.float32))
+    poses = plain["poses"]
+    model = SMPLX(syn.synthetic_smplx_constants(seed=1), batch_size=9)   # run_test's "male" model
+    r = fk_check(poses, seq, model)
+    assert r["per_joint"].shape == (231, 17) and r["mpjpe"].shape == (231,) and isinstance(r["mean"], float)
+    full = np.zeros((231, 55, 3), np.float32)
+    full[:, :22] = poses.reshape(231, 22, 3)
+    jr = sl.smplx_forward(syn.synthetic_smplx_constants(seed=1), full, return_verts=False)[:, SMPLX_TO_COCO]
+    rel = lambda x: x - 0.5 * (x[:, 11:12] + x[:, 12:13])
+    want = np.linalg.norm(rel(jr) - rel(seq.astype(np.float64)), axis=2)
+    # each coordinate within TOL, the root mean of two joints doubling it, sqrt(3) for the norm
+    assert np.abs(r["per_joint"] - want).max() < 4e-4
+    assert np.allclose(r["mpjpe"], r["per_joint"].mean(1)) and np.isclose(r["mean"], r["mpjpe"].mean())
+    checked = run_test(str(src), "synthetic", win_size=64, check=True)
+    assert sorted(checked) == ["coco", "fk_check", "joints", "poses", "vertices"]
+    assert np.array_equal(checked["poses"], plain["poses"]) and np.array_equal(checked["joints"], plain["joints"])
+    assert np.abs(checked["fk_check"]["per_joint"] - want).max() < 4e-4
