@@ -161,8 +161,10 @@ IK_LAYERS = [(3, 64, 1), (64, 64, 1), (64, 128, 2), (128, 128, 1),
              (128, 128, 1), (128, 128, 2), (128, 256, 2), (256, 256, 2)]   # pose_trainer.py:76-83
 
 
-def backbone(x, p: Dict[str, np.ndarray], dtype=np.float64, layers=IK_LAYERS):
-    """StgGcn18.forward, st_gcn_aaai18.py:113-133. x: (N,T,V,C) -> (N,T',V*C')."""
+def backbone(x, p: Dict[str, np.ndarray], dtype=np.float64, layers=IK_LAYERS, taps=None):
+    """StgGcn18.forward, st_gcn_aaai18.py:113-133. x: (N,T,V,C) -> (N,T',V*C').
+    taps: a list that receives every block's output in the same layout,
+    (N,T_l,V*C_l) for block l (the last one is the returned array)."""
     x = np.asarray(x, dtype=dtype)
     N, T, V, C = x.shape
     h = x.transpose(0, 2, 3, 1).reshape(N, V * C, T)                  # :120-121
@@ -172,6 +174,8 @@ def backbone(x, p: Dict[str, np.ndarray], dtype=np.float64, layers=IK_LAYERS):
     for l, (ci, co, s) in enumerate(layers):                           # :128-129
         Ae = A * p[f"backbone.edge_importance.{l}"].astype(dtype)
         h = stgcn_block(h, Ae, p, f"backbone.st_gcn_networks.{l}.", ci, co, s)
+        if taps is not None:
+            taps.append(h.transpose(0, 2, 3, 1).reshape(h.shape[0], h.shape[2], -1))
     h = h.transpose(0, 2, 3, 1)                                        # :131
     return h.reshape(h.shape[0], h.shape[1], -1)                       # :132
 
