@@ -1,6 +1,6 @@
 // common.h — host-side helpers shared by the C-ABI translation units:
-// thread-local last error, HIP error mapping, owning device buffers and the
-// state-dict view of a tik_tensor array.
+// HIP error mapping, owning device buffers, workspaces and the profiler (the
+// last error and the state-dict view of a tik_tensor array: fold.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,58 +15,15 @@
 #include <vector>
 
 #include "../../include/tik.h"
+#include "fold.h"
 
 namespace tik_host {
-
-extern thread_local std::string g_err;
-
-inline int fail(int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
         if (e_ != hipSuccess) return fail(TIK_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
-
-constexpr float BN_EPS = 1e-5f;
-constexpr int TK = 3;   // temporal kernel (pose_trainer.py:85)
-
-struct HostTensor {
-    std::vector<float> v;
-    std::vector<int64_t> shape;
-};
-
-using TensorMap = std::map<std::string, HostTensor>;
-
-inline TensorMap to_map(const tik_tensor* t, int n) {
-    TensorMap m;
-    for (int i = 0; i < n; ++i) {
-        if (!t[i].name) continue;
-        HostTensor h;
-        int64_t numel = 1;
-        for (int d = 0; d < t[i].ndim; ++d) {
-            h.shape.push_back(t[i].shape[d]);
-            numel *= t[i].shape[d];
-        }
-        if (t[i].data) h.v.assign(t[i].data, t[i].data + numel);
-        m[t[i].name] = std::move(h);
-    }
-    return m;
-}
-
-inline const HostTensor* find(const TensorMap& m, const std::string& k) {
-    auto it = m.find(k);
-    return it == m.end() ? nullptr : &it->second;
-}
 
 // Debug hook (TIK_GUARD=1): every device buffer gets 1 MiB guard zones on
 // both sides filled with 0xA5; tik_debug_check_guards() reports the first
@@ -307,7 +264,7 @@ struct ProfRange {
 struct tik_model;
 namespace tik { struct OnlineArgs; }
 namespace tik_host {
-// internal entry points shared by api.cpp and stream.cpp
+// internal entry points shared by model.cpp, forward.cpp and stream.cpp
 int model_reserve_ws(tik_model* m, Workspace& w, int N, int T);
 // the IK forward on workspace w; split = may run as two halves on two streams
 int model_forward_ws(tik_model* m, const float* x, int N, int T, float* poses, hipStream_t st, Workspace& w,

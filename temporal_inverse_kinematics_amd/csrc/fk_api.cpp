@@ -105,8 +105,9 @@ extern "C" {
 int tik_fk_create(const tik_tensor* tensors, int n_tensors, int flags, tik_fk_t* out) {
     if (!tensors || n_tensors <= 0 || !out) return fail(TIK_E_INVALID, "tik_fk_create: null argument");
     *out = nullptr;
-    TensorMap m = to_map(tensors, n_tensors);
-    int rc = TIK_OK;
+    TensorMap m;
+    int rc = to_map(tensors, n_tensors, m);
+    if (rc) return rc;
     const HostTensor* vt = need(m, "v_template", rc);
     const HostTensor* sd = need(m, "shapedirs", rc);
     const HostTensor* pd = need(m, "posedirs", rc);

@@ -89,7 +89,7 @@ hipError_t launch_leaky_dropout_bwd(float* dP, const float* dD, const float* P, 
 hipError_t launch_mse(const float* O, int ldo, const float* T, long long rows, int cols, float* dO, float* loss,
                       hipStream_t st);
 // Eval-mode BatchNorm folded into the forward GEMM operands (the host fold of
-// api.cpp's Layer::build, on the device, from the live parameters): per
+// fold.h's fold_block, on the device, from the live parameters): per
 // channel sc = gamma / sqrt(running_var + eps) (the root in double), sh =
 // beta - running_mean * sc. One descriptor per output tensor dst[rows][cols]:
 //   FOLD_SCALE  dst[co][k] = sc[co] * src[co][k]                       (conv weights, channel = row)

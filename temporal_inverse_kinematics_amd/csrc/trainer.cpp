@@ -60,8 +60,6 @@ struct TLayer {
     int tin = 0, tout = 0;
 };
 
-int round4(int c) { return (c + 3) & ~3; }
-
 tik::Seg seg32(const float* src, const float* w, int cin, int ld, int kt, int stride, int pad, int tin, int ldw) {
     tik::Seg s{src, w, cin, ld, kt, stride, pad, tin, ldw};
     return s;
@@ -631,7 +629,8 @@ extern "C" {
 int tik_trainer_create(const tik_tensor* tensors, int n_tensors, float lr, tik_trainer_t* out) {
     if (!tensors || n_tensors <= 0 || !out || !(lr > 0.f)) return fail(TIK_E_INVALID, "tik_trainer_create: bad arguments");
     *out = nullptr;
-    const TensorMap m = to_map(tensors, n_tensors);
+    TensorMap m;
+    if (const int r = to_map(tensors, n_tensors, m)) return r;
     auto* t = new tik_trainer();
     t->lr = lr;
     std::vector<float> hp, hb;

@@ -94,7 +94,7 @@ def a_eff(sd, l):
 
 
 def is_sparse(sd, l):
-    """What Layer::build decides: every nonzero of A_eff inside the hop <= 2 pattern."""
+    """What fold_block (csrc/fold.h) decides: every nonzero of A_eff inside the hop <= 2 pattern."""
     return not np.any((a_eff(sd, l) != 0) & ~hop2_pattern())
 
 

@@ -157,7 +157,8 @@ def profiled(mod, fn):
 
 
 def expected_labels(k, T, prec, alt=False):
-    """The launches of a k-layer backbone forward at window length T (api.cpp)."""
+    """The launches of a k-layer backbone forward at window length T (csrc/forward.cpp:
+    backbone / backbone_x, with the predicates of Layer in csrc/model.h)."""
     if prec == "fp32":   # cgemm.hip: graph tile + temporal conv per layer
         labs = ["data_bn"]
         for l in range(k):

@@ -40,6 +40,58 @@ def test_library_rejects_bad_args_without_gpu():
         _lib.check(lib.tik_model_create(arr, 1, _lib.ctypes.byref(h)))
 
 
+def _malformed(sd, case):
+    """-> (list of (name, array or None, ndim or None), the name the error must carry)."""
+    l0 = "backbone.st_gcn_networks.0."
+    sd = dict(sd)
+    ndim = {}
+    if case == "rank-1 gcn.conv.weight":
+        name = l0 + "gcn.conv.weight"
+        sd[name] = sd[name].ravel()
+    elif case == "backbone.A null data":
+        name = "backbone.A"
+    elif case == "short edge_importance.0":
+        name = "backbone.edge_importance.0"
+        sd[name] = sd[name][:, :, :16]
+    elif case == "ndim 5":
+        name = l0 + "tcn.2.bias"
+        ndim[name] = 5
+    elif case == "rank-1 pose_regressor.0.weight":
+        name = "pose_regressor.0.weight"
+        sd[name] = sd[name].ravel()
+    elif case == "63 of 64 running_var":
+        name = l0 + "tcn.0"
+        sd[name + ".running_var"] = sd[name + ".running_var"][:63]
+    else:
+        raise ValueError(case)
+    return [(k, None if (case == "backbone.A null data" and k == name) else v, ndim.get(k)) for k, v in sd.items()], name
+
+
+@pytest.mark.parametrize("case", ["rank-1 gcn.conv.weight", "backbone.A null data", "short edge_importance.0", "ndim 5",
+                                  "rank-1 pose_regressor.0.weight", "63 of 64 running_var"])
+def test_model_create_refuses_malformed_state_dict_without_gpu(case, ik_weights):
+    """include/tik.h is a C ABI: a tensor of the wrong rank, with null data, too
+    short, or with ndim past tik_tensor::shape is refused by name on the host,
+    before any shape[i] / v[i] is read and before the first device call."""
+    from temporal_inverse_kinematics_amd import _lib
+    ct = _lib.ctypes
+    lib = _lib.load()
+    tensors, name = _malformed(ik_weights, case)
+    items, keep = [], []
+    for k, v, nd in tensors:
+        a = None if v is None else np.ascontiguousarray(v, dtype=np.float32)
+        shape = list(ik_weights[k].shape if a is None else a.shape)
+        keep += [a, k.encode()]
+        items.append(_lib.TikTensor(keep[-1], None if a is None else a.ctypes.data_as(_lib._F), nd if nd is not None else len(shape),
+                                    (ct.c_int64 * 4)(*(shape + [1] * (4 - len(shape))))))
+    arr = (_lib.TikTensor * len(items))(*items)
+    h = ct.c_void_p(0xdead)
+    rc = lib.tik_model_create(arr, len(items), ct.byref(h))
+    assert rc == _lib.TIK_E_INVALID, (rc, _lib.last_error())
+    assert name in _lib.last_error(), _lib.last_error()
+    assert h.value is None
+
+
 def test_trainer_abi_rejects_bad_args_without_gpu():
     """The training-step C ABI validates before touching the device: a state dict
     without the layer strides is a KeyError, null handles / bad reads ValueError."""
