@@ -1,6 +1,6 @@
 """Config #4: SMPL-X full 55-joint FK + 10475-vertex LBS, batch=4096, 1 GPU.
 
-    python bench_fk.py [--batch 4096] [--steps 10] [--warmup 20] [--joints {all,coco}]
+    python bench_fk.py [--batch 4096] [--steps 10] [--warmup 20] [--joints {all,coco}] [--jacobian] [--refine]
 
 Prints one JSON line: bodies/s, and per kernel (HIP events around every launch
 of a second pass of the same steps, tik_fk_profile) the algorithmic TFLOP/s of
@@ -9,7 +9,10 @@ vertex bytes over HBM; then the oracle CPU baseline. bench.py --full reuses
 measure_fk() for its "fk" key. --joints adds a "joints" key: the mesh-free
 SMPLX.joints (all 144 joints, or the COCO-17 selection) against
 full_forward(return_verts=False) at the same batch, the two legs alternating
-in this process.
+in this process. --jacobian adds a "jacobian" key (SMPLX.joints_jacobian for
+COCO-17 and the 22 body dofs, per-kernel HIP events against the HBM roof of the
+bytes it must move), --refine a "refine" key (one Levenberg-Marquardt iteration
+of refine.refine_poses: Jacobian, residual map, tik_lm_solve, candidate cost).
 """
 import argparse, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -157,6 +160,81 @@ def measure_joints(select="all", batch=4096, steps=10, warmup=20, rounds=5):
                      "full_forward(return_verts=False) builds the body in the handle's workspace"}
 
 
+def _timed(run, steps, warmup, rounds=5):
+    """Median over `rounds` of the HIP-event time of `steps` calls of run(), in ms per call."""
+    import statistics
+    import torch
+    for _ in range(warmup):
+        run()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / steps)
+    return statistics.median(ms), [round(v, 4) for v in ms]
+
+
+def measure_jacobian(batch=4096, steps=10, warmup=20):
+    """SMPLX.joints_jacobian(select="coco", dof=None, return_joints=False) at `batch`
+    bodies on a fresh handle: call time (HIP events, median of 5 rounds), the
+    per-launch profile, and the fk_jacobian launches against the HBM roof of their
+    algorithmic bytes (the (B,51,66) Jacobian out, the chain's outputs in)."""
+    import torch
+    from temporal_inverse_kinematics_amd import _build, synthetic as syn
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    _build.build()
+    m = SMPLX(syn.synthetic_smplx_constants(seed=1), batch_size=batch)
+    pose, betas = syn.synthetic_fk_inputs(batch, seed=1)
+    P, Bt = torch.from_numpy(pose).cuda(), torch.from_numpy(betas).cuda()
+    run = lambda: m.joints_jacobian(P, Bt, select="coco", return_joints=False)
+    med, rounds = _timed(run, steps, warmup)
+    k = _profile(m, run, steps)
+    jk = k.get("fk_jacobian", {})
+    roof_ms = None
+    if jk:
+        roof_ms = jk["gbs"] * jk["avg_ms"] / HBM_PEAK_GBS   # bytes / peak bandwidth
+    return {"select": "coco", "n_dof": 22, "batch": batch, "steps": steps, "warmup": warmup,
+            "jacobian_ms": round(med, 4), "jacobian_ms_rounds": rounds, "workspace_bytes": m.workspace_bytes,
+            "kernels": k, "fk_jacobian_hbm_roof_ms": None if roof_ms is None else round(roof_ms, 4),
+            "fk_jacobian_share_of_hbm_roof": None if not roof_ms else round(roof_ms / jk["avg_ms"], 3),
+            "basis": "median of 5 rounds of `steps` calls between HIP events; kernels: per-launch HIP events "
+                     "(pre-pass and main kernel under one fk_jacobian label); roof = algorithmic bytes / 8 TB/s"}
+
+
+def measure_refine(batch=4096, steps=10, warmup=20):
+    """One LM iteration of refine.refine_poses at `batch` frames: the time of
+    refine_poses(iters=1) minus refine_poses(iters=0) (uploads, the first cost and
+    the copies back are in both), and tik_lm_solve alone on (batch,51,66)."""
+    import numpy as np
+    import torch
+    from temporal_inverse_kinematics_amd import _build, synthetic as syn
+    from temporal_inverse_kinematics_amd.refine import refine_poses
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX, lm_solve
+    _build.build()
+    m = SMPLX(syn.synthetic_smplx_constants(seed=1), batch_size=batch)
+    pose, _ = syn.synthetic_fk_inputs(batch, seed=1)
+    th0 = np.ascontiguousarray(pose[:, :22].reshape(batch, 66))
+    full = torch.zeros((batch, 55, 3), device="cuda")
+    full[:, :22] = torch.from_numpy(pose[:, :22]).cuda() + 0.05
+    kps = m.joints(full, select="coco").cpu().numpy()
+    t1, r1 = _timed(lambda: refine_poses(th0, kps, m, iters=1), steps, warmup)
+    t0, r0 = _timed(lambda: refine_poses(th0, kps, m, iters=0), steps, warmup)
+    jac, joints = m.joints_jacobian(torch.from_numpy(pose).cuda(), select="coco")
+    r = joints.reshape(batch, 51).contiguous()
+    lam = torch.full((batch,), 1e-2, device="cuda")
+    ts, rs = _timed(lambda: lm_solve(jac, r, lam, mu=1e-2), steps, warmup)
+    return {"batch": batch, "steps": steps, "warmup": warmup, "lm_iteration_ms": round(t1 - t0, 4),
+            "refine_iters1_ms": round(t1, 4), "refine_iters0_ms": round(t0, 4), "lm_solve_ms": round(ts, 4),
+            "refine_iters1_ms_rounds": r1, "refine_iters0_ms_rounds": r0, "lm_solve_ms_rounds": rs,
+            "basis": "median of 5 rounds of `steps` calls between HIP events; refine_poses includes its "
+                     "host-to-device uploads and the copy back; lm_solve: (batch,51,66) systems, output allocated per call"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
@@ -165,11 +243,19 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--joints", choices=["all", "coco"], default=None,
                     help="also time the mesh-free SMPLX.joints against full_forward(return_verts=False)")
+    ap.add_argument("--jacobian", action="store_true",
+                    help="also time SMPLX.joints_jacobian (COCO-17, the 22 body dofs)")
+    ap.add_argument("--refine", action="store_true",
+                    help="also time one Levenberg-Marquardt iteration of refine.refine_poses and tik_lm_solve alone")
     a = ap.parse_args()
     from temporal_inverse_kinematics_amd import synthetic as syn
     out = measure_fk(a.batch, a.steps, a.warmup)
     if a.joints:
         out["joints"] = measure_joints(a.joints, a.batch, a.steps, a.warmup)
+    if a.jacobian:
+        out["jacobian"] = measure_jacobian(a.batch, a.steps, a.warmup)
+    if a.refine:
+        out["refine"] = measure_refine(a.batch, a.steps, a.warmup)
     from oracle import smplx_lbs as sl
     c = syn.synthetic_smplx_constants(seed=1)
     pose, betas = syn.synthetic_fk_inputs(16, seed=1)

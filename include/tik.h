@@ -317,14 +317,60 @@ int tik_fk_forward(tik_fk_t fk, const float* full_pose, const float* betas, cons
  * n_sel outside 1..256. */
 int tik_fk_joints(tik_fk_t fk, const float* full_pose, const float* betas, const float* expression,
                   const float* transl, int B, const int* sel_host, int n_sel, float* out, void* stream);
+/* Jacobian of selected joints with respect to the pose, without the mesh:
+ * jac[b][3 s + c][3 d + a] = d joint sel[s] component c / d full_pose[b][dof[d]][a]
+ * at the given inputs; jac is (B, 3 n_sel, 3 n_dof) device fp32, row-major.
+ * sel_host: n_sel (1..256) joint indices as tik_fk_joints (NULL is not allowed
+ * here): the 55 chain joints, the vertex joints and the static landmarks. A
+ * contour landmark picks its vertices by a pose-dependent bin, so its selection
+ * is piecewise constant: an index in that range is TIK_E_INVALID. dof_host:
+ * n_dof (1..55) distinct pose joints in [0, 55), or NULL = joints 0..21 (n_dof
+ * ignored). joints: (B, n_sel, 3) or NULL; when given it is written by
+ * tik_fk_joints itself (the same bits). The derivative is that of the function
+ * tik_fk_joints evaluates (rodrigues_smplx with its 1e-8 shift, pose_mean
+ * added): entries of a chain joint for a dof that is not a strict ancestor of
+ * it are exactly 0. fp32 FMAs in a fixed order for either tik_fk_set_precision
+ * setting: a body's rows are the same bits for any B, any place in the batch
+ * and any selection around a column. Selection and dof list travel in the kernel
+ * arguments: a call uploads nothing and is stream-ordered. Workspace: 3317
+ * floats per body (tik_fk_joints' 1337 + 1980: the rotation derivatives and
+ * angular velocities of 55 dofs, 36 floats each; plus one int per body on a
+ * handle with face contours); the mesh path's buffers are never reserved.
+ * TIK_E_INVALID: null pointers, B <= 0, n_sel outside 1..256, a joint index out
+ * of range or a contour landmark, n_dof outside 1..55, a dof index out of range
+ * or repeated. */
+int tik_fk_joints_jacobian(tik_fk_t fk, const float* full_pose, const float* betas, const float* expression,
+                           const float* transl, int B, const int* sel_host, int n_sel, const int* dof_host, int n_dof,
+                           float* jac, float* joints, void* stream);
 /* Bytes of device workspace the handle currently owns (constants excluded). */
 long long tik_fk_workspace_bytes(tik_fk_t fk);
 /* Per-launch HIP-event profile of tik_fk_forward (fk_chain, fk_blend, fk_skin,
- * fk_landmarks) and tik_fk_joints (fk_chain, fk_joints), as tik_model_profile /
+ * fk_landmarks), tik_fk_joints (fk_chain, fk_joints) and
+ * tik_fk_joints_jacobian (fk_chain, fk_jacobian; when joints are asked for,
+ * tik_fk_joints' own fk_chain, fk_joints come first and the second fk_chain
+ * runs only if no selected joint is made of vertices), as tik_model_profile /
  * _count / _read. */
 int tik_fk_profile(tik_fk_t fk, int max_launches);
 int tik_fk_profile_count(tik_fk_t fk);
 int tik_fk_profile_read(tik_fk_t fk, int i, char* label, int label_len, float* ms, double* flops, double* bytes);
+
+/* ------------------------------------------------------------------------
+ * Batched damped least squares (the Levenberg-Marquardt step of refine.py):
+ * for each body b it solves
+ *   (J^T W J + (mu + lambda[b]) I) delta = -(J^T W r + mu prior)
+ * jac (B,m,n), r (B,m), prior (B,n) or NULL (= 0), row_w (m) non-negative row
+ * weights W = diag(row_w) or NULL (= 1), lambda (B), delta (B,n); all device
+ * fp32. 1 <= n <= 165, 1 <= m <= 768, mu >= 0; mu + lambda[b] > 0 is the
+ * caller's promise. No handle and no workspace: one workgroup per body builds
+ * the normal matrix in LDS (fp32 FMAs, rows ascending), factors it (Cholesky)
+ * and runs both triangular solves in the same launch; only delta is written.
+ * A pivot that is not positive writes NaN into that body's delta and nothing
+ * else. A body's delta is the same bits for any B. Stream-ordered.
+ * TIK_E_INVALID: null jac / r / lambda / delta, B <= 0, n or m out of range,
+ * mu negative or NaN.
+ * ---------------------------------------------------------------------- */
+int tik_lm_solve(const float* jac, const float* r, const float* prior, const float* row_w, const float* lambda,
+                 float mu, int B, int m, int n, float* delta, void* stream);
 
 #ifdef __cplusplus
 }

@@ -90,4 +90,37 @@ struct FkJointsArgs {
 };
 hipError_t launch_fk_joints(const FkJointsArgs& a, hipStream_t st);
 
+// Jacobian of selected joints with respect to the pose (fk_jacobian.hip), after
+// fk_chain_kernel wrote feat, ajt and the chain joints. Two launches:
+//   fk_jac_pre_kernel   per (body, dof joint j): dR_a = d R_j / d theta_a (a = 0..2, the derivative of
+//                       rodrigues_smplx as written) and the world-frame angular velocity
+//                       omega_a = axial(G_parent.R dR_a G_j.R^T), into jw
+//   fk_jacobian_kernel  lane = body, wave = output column s; for every dof the 3x3 block
+//                       d joint sel[s] / d theta_j, stored as three runs of 3 floats in the body's rows
+// jw is dof-major so that lane = body reads are coalesced: value q of dof d of body b at
+// jw[(d * FKJAC_PER_DOF + q) * B + b], q < 27 dR_a[m] (9 a + m), 27 <= q < 36 omega_a[c] (27 + 3 a + c).
+constexpr int FKJAC_PER_DOF = 36;
+constexpr int FKJAC_WS = 55 * FKJAC_PER_DOF;   // floats of jw per body (include/tik.h: 1337 + 1980)
+struct FkJacArgs {
+    int B, n_sel, n_dof, nextra, nz;   // nextra: joints 55 .. 55 + nextra are one vertex, later ones three; nz as FkJointsArgs
+    const float* pose;       // (B,55,3)
+    const float* pose_mean;  // (55,3)
+    const int* parents;      // (55)
+    const unsigned long long* anc;   // (55) bit j of anc[k]: j is k or an ancestor of k
+    const float* feat;       // (B,512)
+    const float* ajt;        // (55,B,12)
+    const float* jchain;     // (B,55,3), transl included
+    const float* transl;     // (B,3) or null
+    const float* PT;         // [3V][512]
+    const float* WT;         // [V][64]
+    const int2* nzw;         // (V,nz) or null
+    const int* pick_v;       // as FkJointsArgs
+    const float* pick_w;
+    float* jw;               // (n_dof, FKJAC_PER_DOF, B)
+    float* jac;              // (B, 3 n_sel, 3 n_dof)
+    unsigned short sel[FKJ_MAX_SEL];
+    unsigned char dof[56];
+};
+hipError_t launch_fk_jacobian(const FkJacArgs& a, hipStream_t st);
+
 }  // namespace tik

@@ -84,6 +84,10 @@ struct tik_fk {
     // contour's by bin; workspace: the chain's (B,55,3) joints (feat, ajt, dyn_bin are shared)
     DevIBuf pick_v, dyn_v;
     DevBuf pick_w, jchain;
+    // tik_fk_joints_jacobian (fk_jacobian.hip): bit j of anc[k] = joint j is k or an ancestor of k;
+    // workspace: dR and omega of every dof (FKJAC_WS floats per body)
+    DevArray<unsigned long long> anc;
+    DevBuf jacw;
     Profiler prof;     // per-launch HIP events (tik_fk_profile; bench.py's FK roofline)
     bool profiling = false;
 };
@@ -279,6 +283,14 @@ int tik_fk_create(const tik_tensor* tensors, int n_tensors, int flags, tik_fk_t*
                 for (int i = 0; i < 3; ++i) dv[3 * e + i] = hfaces[3 * hdf[e] + i];
         }
         if ((rc = fk->pick_v.upload(pv)) || (rc = fk->pick_w.upload(pw)) || (rc = fk->dyn_v.upload(dv))) {
+            delete fk;
+            return rc;
+        }
+    }
+    {   // ancestor-or-self masks of the Jacobian path (parents are topologically ordered)
+        std::vector<unsigned long long> anc(NJ);
+        for (int k = 0; k < NJ; ++k) anc[k] = (1ull << k) | (hpar[k] >= 0 ? anc[hpar[k]] : 0ull);
+        if ((rc = fk->anc.upload(anc))) {
             delete fk;
             return rc;
         }
@@ -512,10 +524,81 @@ int tik_fk_joints(tik_fk_t fk, const float* full_pose, const float* betas, const
     return TIK_OK;
 }
 
+int tik_fk_joints_jacobian(tik_fk_t fk, const float* full_pose, const float* betas, const float* expression,
+                           const float* transl, int B, const int* sel_host, int n_sel, const int* dof_host, int n_dof,
+                           float* jac, float* joints, void* stream) {
+    if (!fk || !full_pose || !sel_host || !jac || B <= 0) return fail(TIK_E_INVALID, "tik_fk_joints_jacobian: bad arguments");
+    if (n_sel < 1 || n_sel > tik::FKJ_MAX_SEL)
+        return fail(TIK_E_INVALID, "tik_fk_joints_jacobian: n_sel must be 1..%d, got %d", tik::FKJ_MAX_SEL, n_sel);
+    if (dof_host && (n_dof < 1 || n_dof > NJ))
+        return fail(TIK_E_INVALID, "tik_fk_joints_jacobian: n_dof must be 1..%d, got %d", NJ, n_dof);
+    hipStream_t st = (hipStream_t)stream;
+    tik::FkJacArgs k{};   // selection and dof list travel in the kernel arguments: nothing is uploaded per call
+    const int nstatic = NJ + fk->nextra + fk->nlmk;
+    int npick = 0;
+    for (int s = 0; s < n_sel; ++s) {
+        const int j = sel_host[s];
+        if (j < 0 || j >= fk->njoints)
+            return fail(TIK_E_INVALID, "tik_fk_joints_jacobian: joint index %d out of range [0, %d)", j, fk->njoints);
+        if (j >= nstatic)
+            return fail(TIK_E_INVALID, "tik_fk_joints_jacobian: joint %d is a contour landmark: its vertices are picked by a "
+                        "pose-dependent bin (piecewise constant), so it has no Jacobian here", j);
+        k.sel[s] = (unsigned short)j;
+        npick += j < NJ ? 0 : j < NJ + fk->nextra ? 1 : 3;
+    }
+    k.n_dof = dof_host ? n_dof : 22;
+    unsigned long long seen = 0;
+    for (int d = 0; d < k.n_dof; ++d) {
+        const int j = dof_host ? dof_host[d] : d;
+        if (j < 0 || j >= NJ) return fail(TIK_E_INVALID, "tik_fk_joints_jacobian: dof joint %d out of range [0, %d)", j, NJ);
+        if ((seen >> j) & 1ull) return fail(TIK_E_INVALID, "tik_fk_joints_jacobian: dof joint %d repeated", j);
+        seen |= 1ull << j;
+        k.dof[d] = (unsigned char)j;
+    }
+    // the joints first, on tik_fk_joints itself (its bits, its "fk_chain" / "fk_joints" launches)
+    int rc;
+    if (joints && (rc = tik_fk_joints(fk, full_pose, betas, expression, transl, B, sel_host, n_sel, joints, stream))) return rc;
+    // workspace: tik_fk_joints' 1337 floats per body + FKJAC_WS (include/tik.h)
+    if ((rc = fk->jchain.reserve((size_t)B * NJ * 3)) || (fk->contour && (rc = fk->dyn_bin.reserve((size_t)B))) ||
+        (rc = fk->feat.reserve((size_t)B * KP)) || (rc = fk->ajt.reserve((size_t)B * NJ * 12)) ||
+        (rc = fk->jacw.reserve((size_t)B * tik::FKJAC_WS)))
+        return rc;
+    Profiler* pf = fk->profiling ? &fk->prof : nullptr;
+    // the chain with the feature and the transforms forced on, unless tik_fk_joints above already ran it
+    // that way (it does when a selected joint is made of vertices)
+    if (!joints || npick == 0) {
+        tik::FkChainArgs c{};
+        c.B = B; c.nb = fk->nb; c.ne = fk->ne; c.kp = KP; c.kj = KJ; c.njoints = NJ; c.nchain = fk->nchain;
+        c.pose = full_pose; c.betas = betas; c.expr = expression; c.transl = transl; c.pose_mean = fk->pose_mean.p;
+        c.parents = fk->parents.p; c.chain = fk->chain.p; c.jt = fk->jt.p; c.jd = fk->jd.p;
+        c.feat = fk->feat.p; c.ablk = nullptr; c.arows = 12; c.ajt = fk->ajt.p;
+        c.joints = fk->jchain.p; c.dyn_bin = fk->contour ? fk->dyn_bin.p : nullptr;
+        c.depth = fk->depth.p; c.maxdepth = fk->maxdepth;
+        ProfRange pr(pf, "fk_chain", 0.0, 4.0 * (double)B * (NJ * 3 + 20 + NJ * 3 + KP + 12 * NJ), st);
+        HIP_TRY(tik::launch_fk_chain(c, st));
+    }
+    k.B = B; k.n_sel = n_sel; k.nextra = fk->nextra;
+    k.nz = fk->dense ? 0 : fk->sp_nz;
+    k.pose = full_pose; k.pose_mean = fk->pose_mean.p; k.parents = fk->parents.p; k.anc = fk->anc.p;
+    k.feat = fk->feat.p; k.ajt = fk->ajt.p; k.jchain = fk->jchain.p; k.transl = transl;
+    k.PT = fk->PT.p; k.WT = fk->WT.p; k.nzw = reinterpret_cast<const int2*>(fk->nzw.p);
+    k.pick_v = fk->pick_v.p; k.pick_w = fk->pick_w.p;
+    k.jw = fk->jacw.p; k.jac = jac;
+    // algorithmic, per (vertex evaluation, dof): the masked skinning sum, three cross products, the
+    // 27-term pose-blend derivative and its 3x3 transform; per vertex evaluation the 3 dot products of
+    // 507; bytes: the Jacobian out, feat / A_j / chain joints in, the dof workspace written and read
+    const double terms = k.nz ? k.nz : NJ, nd = k.n_dof;
+    ProfRange pr(pf, "fk_jacobian", 2.0 * B * (npick * (3.0 * 507 + 12.0 * terms + nd * (4.0 * terms + 27 + 81 + 27)) +
+                                               9.0 * n_sel * nd + 150.0 * nd),
+                 4.0 * B * (9.0 * n_sel * nd + KP + 12 * NJ + 3 * NJ + 2.0 * tik::FKJAC_PER_DOF * nd), st);
+    HIP_TRY(tik::launch_fk_jacobian(k, st));
+    return TIK_OK;
+}
+
 long long tik_fk_workspace_bytes(tik_fk_t fk) {
     if (!fk) return fail(TIK_E_INVALID, "null fk handle");
     return (long long)(4 * (fk->feat.n + fk->ablk.n + fk->vposed.n + fk->verts_ws.n + fk->ajt.n + fk->zero_transl.n +
-                            fk->dyn_bin.n + fk->jchain.n) + 2 * fk->trash.n);
+                            fk->dyn_bin.n + fk->jchain.n + fk->jacw.n) + 2 * fk->trash.n);
 }
 
 int tik_fk_profile(tik_fk_t fk, int max_launches) {

@@ -6,7 +6,7 @@ reference, each window's output frame 0 is the solution for frame idx
 
 CLI (README.md:24-26):
     python -m temporal_inverse_kinematics_amd.inference <moveai_3d.npz> [SMPLX_DIR]
-        [--ckpt model.ckpt] [--win-size 64] [--out poses.npy] [--check]
+        [--ckpt model.ckpt] [--win-size 64] [--out poses.npy] [--check] [--refine N]
 Without --ckpt the seeded synthetic weights are used (the trained checkpoint
 is not distributed with the reference: .MISSING_LARGE_BLOBS:2).
 """
@@ -80,9 +80,16 @@ def fk_check(poses, seq_3d_kps, smplx_model, betas=None) -> dict:
 
 
 def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = None, win_size: int = 64,
-             device="cuda", check: bool = False):
+             device="cuda", check: bool = False, refine: int = 0):
     """inference.run_test:110-145: moveai npz -> COCO -> IK -> (optional) SMPL-X FK.
-    check=True (with an SMPL-X dir): the result gains "fk_check" (fk_check above)."""
+    check=True (with an SMPL-X dir): the result gains "fk_check" (fk_check above).
+    refine=N > 0 (with an SMPL-X dir): N Levenberg-Marquardt iterations on the
+    solved poses (refine.refine_poses); the result gains "poses_refined" and,
+    with check, "fk_check_refined". refine=0 leaves every output as it is."""
+    if refine < 0:
+        raise ValueError(f"refine must be >= 0, got {refine}")
+    if refine and not smplx_dir:
+        raise ValueError("refine needs an SMPL-X dir (or 'synthetic'): the refinement runs the FK")
     d = np.load(npz_path, allow_pickle=False)
     # the moveai_3d -> COCO conversion on the device (one gather kernel, bit-identical to the host form)
     seq = kp.moveai3d_to_coco_device(torch.as_tensor(np.ascontiguousarray(d["joints_3d"], dtype=np.float32),
@@ -104,10 +111,15 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
         result.update(joints=joints, vertices=verts)
         if check:
             result["fk_check"] = fk_check(poses, result["coco"], models["male"])
+        if refine:
+            from .refine import refine_poses
+            result["poses_refined"] = refine_poses(poses, result["coco"], models["male"], iters=refine)["poses"]
+            if check:
+                result["fk_check_refined"] = fk_check(result["poses_refined"], result["coco"], models["male"])
     return result
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("npz")
     p.add_argument("smplx_dir", nargs="?")
@@ -116,13 +128,27 @@ def main(argv=None):
     p.add_argument("--out")
     p.add_argument("--check", action="store_true",
                    help="with SMPLX_DIR: compare the FK joints of the solved poses with the input keypoints")
+    p.add_argument("--refine", type=int, default=0, metavar="N",
+                   help="with SMPLX_DIR: N Levenberg-Marquardt iterations pulling the FK joints of the solved "
+                        "poses onto the keypoints (--out then saves the refined poses)")
+    return p
+
+
+def main(argv=None):
+    p = build_parser()
     a = p.parse_args(argv)
-    r = run_test(a.npz, a.smplx_dir, a.ckpt, a.win_size, check=a.check)
+    if a.refine < 0 or (a.refine and not a.smplx_dir):
+        p.error("--refine N needs N >= 0 and an SMPLX_DIR")
+    r = run_test(a.npz, a.smplx_dir, a.ckpt, a.win_size, check=a.check, refine=a.refine)
     if a.out:
-        np.save(a.out, r["poses"])
+        np.save(a.out, r.get("poses_refined", r["poses"]))
     print(f"solved {r['poses'].shape[0]} frames -> poses {r['poses'].shape}")
     if "fk_check" in r:
         print(f"FK check: mean root-relative joint distance {r['fk_check']['mean']:.6f}")
+    if "poses_refined" in r:
+        print(f"refined {r['poses_refined'].shape[0]} frames with {a.refine} LM iterations")
+    if "fk_check_refined" in r:
+        print(f"FK check: before {r['fk_check']['mean']:.6f} -> after {r['fk_check_refined']['mean']:.6f}")
     return 0
 
 

@@ -103,6 +103,60 @@ def resolve_select(select, num_joints: int):
     return sel
 
 
+NUM_POSE_JOINTS = 55
+DEFAULT_DOF = tuple(range(22))   # global orient + 21 body joints: the 66 values the IK solves
+LM_MAX_N, LM_MAX_M = 165, 768    # include/tik.h, tik_lm_solve
+
+
+def resolve_dof(dof):
+    """A dof list -> list of pose joints the Jacobian is taken with respect to.
+    `dof`: None (joints 0..21) or a sequence of 1..55 distinct ints in [0, 55).
+    ValueError otherwise; the library is not touched."""
+    if dof is None:
+        return list(DEFAULT_DOF)
+    if isinstance(dof, str):
+        raise ValueError(f"unknown dof list {dof!r}; expected None or a sequence of pose joint indices")
+    d = [int(j) for j in dof]
+    if not 1 <= len(d) <= NUM_POSE_JOINTS:
+        raise ValueError(f"a dof list has 1..{NUM_POSE_JOINTS} entries, got {len(d)}")
+    for j in d:
+        if not 0 <= j < NUM_POSE_JOINTS:
+            raise ValueError(f"dof joint {j} out of range [0, {NUM_POSE_JOINTS})")
+    if len(set(d)) != len(d):
+        raise ValueError("dof joints must be distinct")
+    return d
+
+
+def lm_solve(jac: torch.Tensor, r: torch.Tensor, lam: torch.Tensor, mu: float = 0.0, prior=None, row_weight=None):
+    """One damped least-squares step per body (tik_lm_solve):
+    (J^T W J + (mu + lam[b]) I) delta = -(J^T W r + mu prior). jac (B,m,n),
+    r (B,m), lam (B), prior (B,n) or None (zero), row_weight (m) non-negative
+    or None (one); contiguous float32 on the device. n <= 165, m <= 768,
+    mu >= 0; mu + lam[b] > 0 is the caller's promise (a matrix that is not
+    positive gives a NaN row, nothing else). -> delta (B,n)."""
+    if jac.dim() != 3:
+        raise ValueError(f"jac must be (B, m, n), got {tuple(jac.shape)}")
+    B, m, n = (int(s) for s in jac.shape)
+    if B < 1 or not 1 <= n <= LM_MAX_N or not 1 <= m <= LM_MAX_M:
+        raise ValueError(f"lm_solve: need B >= 1, 1 <= m <= {LM_MAX_M}, 1 <= n <= {LM_MAX_N}; got {(B, m, n)}")
+    if tuple(r.shape) != (B, m):
+        raise ValueError(f"r must be {(B, m)}, got {tuple(r.shape)}")
+    if tuple(lam.shape) != (B,):
+        raise ValueError(f"lam must be {(B,)}, got {tuple(lam.shape)}")
+    if prior is not None and tuple(prior.shape) != (B, n):
+        raise ValueError(f"prior must be {(B, n)}, got {tuple(prior.shape)}")
+    if row_weight is not None and tuple(row_weight.shape) != (m,):
+        raise ValueError(f"row_weight must be {(m,)}, got {tuple(row_weight.shape)}")
+    mu = float(mu)
+    if not mu >= 0.0:
+        raise ValueError(f"mu must be >= 0, got {mu}")
+    _lib.require_gpu(jac, r, lam, prior, row_weight)
+    delta = torch.empty((B, n), device=jac.device, dtype=torch.float32)
+    _lib.check(_lib.load().tik_lm_solve(jac.data_ptr(), r.data_ptr(), _lib.ptr(prior), _lib.ptr(row_weight),
+                                        lam.data_ptr(), mu, B, m, n, delta.data_ptr(), _lib.stream_of(jac)), "lm_solve")
+    return delta
+
+
 def split_pose156(P: torch.Tensor, apply_root_rot: bool = True) -> torch.Tensor:
     """AMASS pose rows (R,156) [root 3 | body 63 | lhand 45 | rhand 45] on the
     device -> full_pose (R,55,3) (jaw and eyes zero), smpl_util.py:58-66."""
@@ -143,6 +197,8 @@ class SMPLX:
         self.precision = precision if precision is not None else ("fp32" if env in ("fp32", "f32") else "bf16x3")
         self.num_joints = _lib.check(lib.tik_fk_num_joints(self._h))
         self.num_verts = _lib.check(lib.tik_fk_num_verts(self._h))
+        # joints below this index have a Jacobian (chain, vertex joints, static landmarks); the contour follows
+        self.num_static_joints = NUM_POSE_JOINTS + len(constants["extra_verts"]) + len(constants["lmk_faces_idx"])
 
     def __del__(self):
         try:
@@ -210,6 +266,38 @@ class SMPLX:
                                              _lib.ptr(args[2]), B, csel, n, out.data_ptr(), _lib.stream_of(fp)),
                    "SMPLX.joints")
         return out
+
+    def joints_jacobian(self, full_pose: torch.Tensor, betas=None, expression=None, transl=None, select="coco",
+                        dof=None, return_joints: bool = True):
+        """full_pose (B,55,3) device -> (jac (B, 3n, 3k), joints (B,n,3) or None):
+        jac[b, 3s+c, 3d+a] = d joint select[s] component c / d full_pose[b, dof[d], a]
+        (tik_fk_joints_jacobian, fp32 FMAs for either `precision`). select: "coco"
+        or a sequence of joint indices below num_static_joints (a contour
+        landmark's vertices change with the pose by bins: no Jacobian; None is not
+        allowed). dof: None (joints 0..21) or distinct pose joints in [0, 55).
+        joints, when asked for, are bit for bit those of joints(select=select)."""
+        if select is None:
+            raise ValueError("joints_jacobian needs a selection ('coco' or joint indices); "
+                             "all joints would include the contour landmarks, which have no Jacobian")
+        sel = resolve_select(select, self.num_joints)
+        for j in sel:
+            if j >= self.num_static_joints:
+                raise ValueError(f"joint {j} is a contour landmark (its vertices are picked by a pose-dependent bin): "
+                                 f"no Jacobian; select joints below {self.num_static_joints}")
+        d = resolve_dof(dof)
+        fp = full_pose.reshape(-1, 55, 3).contiguous()
+        B = fp.shape[0]
+        args = [t.contiguous() if t is not None else None for t in (betas, expression, transl)]
+        _lib.require_gpu(fp, *args)
+        n, k = len(sel), len(d)
+        jac = torch.empty((B, 3 * n, 3 * k), device=fp.device, dtype=torch.float32)
+        joints = torch.empty((B, n, 3), device=fp.device, dtype=torch.float32) if return_joints else None
+        csel = (_lib.ctypes.c_int * n)(*sel)
+        cdof = None if dof is None else (_lib.ctypes.c_int * k)(*d)
+        _lib.check(_lib.load().tik_fk_joints_jacobian(self._h, fp.data_ptr(), _lib.ptr(args[0]), _lib.ptr(args[1]),
+                                                      _lib.ptr(args[2]), B, csel, n, cdof, k, jac.data_ptr(),
+                                                      _lib.ptr(joints), _lib.stream_of(fp)), "SMPLX.joints_jacobian")
+        return jac, joints
 
     @property
     def workspace_bytes(self) -> int:

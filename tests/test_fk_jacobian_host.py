@@ -1,0 +1,118 @@
+"""Host side of the FK Jacobian / LM refinement: the dof resolver, the
+ValueError paths of SMPLX.joints_jacobian, lm_solve and refine_poses (reached
+without loading the library), the --refine argument, and the C ABI's two new
+entry points (declared, exported, refusing bad arguments before any device
+call). No GPU."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import REPO
+
+
+@pytest.fixture
+def no_library(monkeypatch):
+    from temporal_inverse_kinematics_amd import _lib
+
+    def refuse(*a, **k):
+        raise AssertionError("the validators must not touch the library")
+    monkeypatch.setattr(_lib, "load", refuse)
+
+
+def _bare_model():
+    """An SMPLX object without a handle: what the validators read, nothing else."""
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    m = object.__new__(SMPLX)
+    m.num_joints, m.num_static_joints, m.device = 144, 127, torch.device("cpu")
+    return m
+
+
+def test_resolve_dof(no_library):
+    from temporal_inverse_kinematics_amd.smplx_fk import resolve_dof
+    assert resolve_dof(None) == list(range(22))
+    assert resolve_dof([5]) == [5]
+    assert resolve_dof(np.array([54, 0, 3])) == [54, 0, 3]
+    assert resolve_dof(range(55)) == list(range(55))
+    for bad in ([], [55], [-1], [0, 0], list(range(55)) + [1], "body"):
+        with pytest.raises(ValueError):
+            resolve_dof(bad)
+
+
+def test_joints_jacobian_validates_before_the_library(no_library):
+    m = _bare_model()
+    pose = torch.zeros((2, 55, 3))
+    for kw in ({"select": None}, {"select": "body25"}, {"select": [144]}, {"select": []}, {"select": [0] * 257},
+               {"select": [0, 127]}, {"select": [143]}, {"dof": [55]}, {"dof": [1, 1]}, {"dof": []}):
+        with pytest.raises(ValueError):
+            m.joints_jacobian(pose, **kw)
+    with pytest.raises(ValueError, match="contour"):
+        m.joints_jacobian(pose, select=[130])
+
+
+def test_lm_solve_validates_before_the_library(no_library):
+    from temporal_inverse_kinematics_amd.smplx_fk import lm_solve
+    J, r, lam = torch.zeros((2, 5, 4)), torch.zeros((2, 5)), torch.ones(2)
+    bad = [dict(jac=J[0]), dict(r=r[:, :4]), dict(lam=lam[:1]), dict(mu=-0.5), dict(mu=float("nan")),
+           dict(prior=torch.zeros((2, 5))), dict(row_weight=torch.zeros(4)), dict(jac=torch.zeros((2, 5, 166))),
+           dict(jac=torch.zeros((2, 769, 4)), r=torch.zeros((2, 769))), dict(jac=torch.zeros((0, 5, 4)))]
+    for kw in bad:
+        a = dict(jac=J, r=r, lam=lam)
+        a.update(kw)
+        with pytest.raises(ValueError):
+            lm_solve(**a)
+    with pytest.raises(RuntimeError, match="GPU"):   # valid shapes on the CPU: refused, no fallback
+        lm_solve(J, r, lam)
+
+
+def test_refine_poses_validates_before_the_library(no_library):
+    from temporal_inverse_kinematics_amd.refine import refine_poses
+    m = _bare_model()
+    poses, kps = np.zeros((3, 66), np.float32), np.zeros((3, 17, 3), np.float32)
+    for kw in (dict(prior_weight=0), dict(prior_weight=-1e-3), dict(prior_weight=float("nan")), dict(iters=-1),
+               dict(lam0=0.0), dict(joint_weight=np.ones(16)), dict(joint_weight=-np.ones(17))):
+        with pytest.raises(ValueError):
+            refine_poses(poses, kps, m, **kw)
+    with pytest.raises(ValueError):
+        refine_poses(poses[:, :60], kps, m)
+    with pytest.raises(ValueError):
+        refine_poses(poses, kps[:2], m)
+
+
+def test_refine_argument_parses(no_library):
+    from temporal_inverse_kinematics_amd import inference
+    p = inference.build_parser()
+    a = p.parse_args(["seq.npz", "synthetic", "--refine", "5", "--check"])
+    assert a.refine == 5 and a.check and a.smplx_dir == "synthetic"
+    assert p.parse_args(["seq.npz"]).refine == 0
+    with pytest.raises(SystemExit):
+        p.parse_args(["seq.npz", "--refine", "many"])
+    with pytest.raises(SystemExit):
+        inference.main(["seq.npz", "--refine", "2"])          # no SMPL-X dir
+    with pytest.raises(ValueError):
+        inference.run_test("seq.npz", None, refine=2)
+    with pytest.raises(ValueError):
+        inference.run_test("seq.npz", "synthetic", refine=-1)
+
+
+def test_header_declares_and_library_exports_the_entry_points():
+    from temporal_inverse_kinematics_amd import _build, _lib
+    txt = open(os.path.join(REPO, "include", "tik.h")).read()
+    for name in ("tik_fk_joints_jacobian", "tik_lm_solve"):
+        assert re.search(rf"^int {name}\(", txt, re.M), name
+        assert name in _lib.SIGNATURES
+    assert "3317" in txt and "1337" in txt          # the workspace budget is written down beside tik_fk_joints'
+    _build.build()
+    lib = _lib.load()
+    assert hasattr(lib, "tik_fk_joints_jacobian") and hasattr(lib, "tik_lm_solve")
+    # refused on the host, before any device call
+    assert lib.tik_fk_joints_jacobian(None, None, None, None, None, 1, None, 0, None, 0, None, None, None) == _lib.TIK_E_INVALID
+    assert "tik_fk_joints_jacobian" in _lib.last_error()
+    one = (_lib.ctypes.c_float * 4)()
+    p = _lib.ctypes.addressof(one)
+    assert lib.tik_lm_solve(None, p, None, None, p, 0.0, 1, 1, 1, p, None) == _lib.TIK_E_INVALID
+    for B, m, n, mu in ((0, 1, 1, 0.0), (1, 0, 1, 0.0), (1, 769, 1, 0.0), (1, 1, 0, 0.0), (1, 1, 166, 0.0), (1, 1, 1, -1.0)):
+        assert lib.tik_lm_solve(p, p, None, None, p, mu, B, m, n, p, None) == _lib.TIK_E_INVALID, (B, m, n, mu)
+        assert "tik_lm_solve" in _lib.last_error()
