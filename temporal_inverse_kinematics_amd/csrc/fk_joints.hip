@@ -35,7 +35,7 @@ namespace fkj {
 constexpr int TB = FKJ_TB;           // bodies per tile
 constexpr int JW = 8;                // output columns (waves) per workgroup
 constexpr int KC = 64;               // k per staged chunk
-constexpr int KP = 512;              // feature row length (fk_api.cpp KP)
+constexpr int KP = 512;              // feature row length (fk_fold.h KP)
 constexpr int LDF = TB + 1;          // LDS row stride of the transposed chunk (the staging writes spread over banks)
 constexpr int NLD = KC * TB / 4 / (64 * JW);   // f32x4 staging loads per thread per chunk
 static_assert(NLD * 4 * 64 * JW == KC * TB, "chunk must divide over the workgroup");

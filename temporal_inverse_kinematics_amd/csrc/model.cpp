@@ -132,7 +132,7 @@ int model_online_fill(tik_model* m, tik::OnlineArgs& a) {
 
 extern "C" {
 
-int tik_model_create(const tik_tensor* tensors, int n_tensors, tik_model_t* out) {
+int tik_model_create(const tik_tensor* tensors, int n_tensors, tik_model_t* out) try {
     if (!tensors || n_tensors <= 0 || !out) return fail(TIK_E_INVALID, "tik_model_create: null argument");
     *out = nullptr;
     // host: a refused state dict allocates nothing and never touches the GPU
@@ -165,7 +165,7 @@ int tik_model_create(const tik_tensor* tensors, int n_tensors, tik_model_t* out)
     apply_env(md.get());
     *out = md.release();
     return TIK_OK;
-}
+} catch (const std::bad_alloc&) { return fail(TIK_E_NOMEM, "tik_model_create: out of host memory"); }   // no exception crosses the C ABI
 
 int tik_model_destroy(tik_model_t m) {
     if (m) model_release(m);   // freed now, or when its last online-IK stream is destroyed

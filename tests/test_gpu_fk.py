@@ -150,7 +150,7 @@ def test_fk_sparse_skinning(consts, monkeypatch, nzmax):
 @pytest.mark.parametrize("B", [1, 1025, 2500, 4096])
 def test_fk_chunk_pipeline_batch_invariant(consts, B):
     """Batches of more than one 1024-body chunk run blend + skinning per chunk,
-    the chunks alternating between two HIP streams (fk_api.cpp): every body's
+    the chunks alternating between two HIP streams (fk_forward.cpp): every body's
     vertices and joints are bit-identical to the same body solved alone (the
     chunking only partitions rows), at one body, a chunk plus one, a ragged
     last chunk and config #4's batch; sampled bodies against the oracle."""

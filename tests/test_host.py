@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import fk_constants_cases as fk_cases
 from conftest import REPO, golden
 
 
@@ -87,6 +88,30 @@ def test_model_create_refuses_malformed_state_dict_without_gpu(case, ik_weights)
     arr = (_lib.TikTensor * len(items))(*items)
     h = ct.c_void_p(0xdead)
     rc = lib.tik_model_create(arr, len(items), ct.byref(h))
+    assert rc == _lib.TIK_E_INVALID, (rc, _lib.last_error())
+    assert name in _lib.last_error(), _lib.last_error()
+    assert h.value is None
+
+
+@pytest.mark.parametrize("case", fk_cases.ABI_CASES)
+def test_fk_create_refuses_malformed_constants_without_gpu(case):
+    """The SMPL-X constants cross the same C ABI: a tensor of the wrong rank or
+    shape, with null data or too short is refused by name on the host
+    (csrc/fk_fold.h), before any shape[i] / v[i] is read and before the first
+    device call: with no device, a constant set that got as far as an upload
+    would come back as an allocation failure instead."""
+    from temporal_inverse_kinematics_amd import _lib
+    ct = _lib.ctypes
+    lib = _lib.load()
+    tensors, name = fk_cases.malformed(fk_cases.small_constants(), case)
+    items, keep = [], []
+    for k, a, has in tensors:
+        keep += [a, k.encode()]
+        items.append(_lib.TikTensor(keep[-1], a.ctypes.data_as(_lib._F) if has else None, a.ndim,
+                                    (ct.c_int64 * 4)(*(list(a.shape) + [1] * (4 - a.ndim)))))
+    arr = (_lib.TikTensor * len(items))(*items)
+    h = ct.c_void_p(0xdead)
+    rc = lib.tik_fk_create(arr, len(items), 1, ct.byref(h))
     assert rc == _lib.TIK_E_INVALID, (rc, _lib.last_error())
     assert name in _lib.last_error(), _lib.last_error()
     assert h.value is None
