@@ -57,23 +57,30 @@ def _bn(x, P, B, name):
                         P[name + ".bias"], training=True, momentum=BN_MOMENTUM, eps=BN_EPS)
 
 
-def _relu(v, key, relu_masks):
+def _relu(v, key, relu_masks, record=None):
     """ReLU, or (relu_masks given) the product with an externally supplied 0/1
     mask: the backward then takes the same branch at every element as the
     implementation whose masks they are (a pre-activation within rounding of 0
-    may land on either side in two correct fp32 implementations)."""
+    may land on either side in two correct fp32 implementations).
+    record: optional dict that receives the branch taken, (v > 0) as 0/1 fp32."""
+    if record is not None:
+        record[key] = (v.detach() > 0).float()
     if relu_masks is None:
         return F.relu(v)
-    return v * relu_masks[key]
+    return v * relu_masks[key].to(v.dtype)
 
 
 def forward(P: Dict[str, torch.Tensor], B: Dict[str, torch.Tensor], x: torch.Tensor, mask: torch.Tensor,
-            layers=IK_LAYERS, taps=None, relu_masks=None) -> torch.Tensor:
+            layers=IK_LAYERS, taps=None, relu_masks=None, dtype=torch.float32, record=None) -> torch.Tensor:
     """Train-mode PoseRegressor.forward (pose_trainer.py:94-133) -> poses (N,T',66).
     taps: optional list that receives every block's output (gradient retained).
     relu_masks: optional {("H", l), ("O", l): (N,C,T,V) 0/1, "P": (N*T', 512) 0/1}
-    fixing the branch of every ReLU / LeakyReLU (see _relu)."""
+    fixing the branch of every ReLU / LeakyReLU (see _relu).
+    dtype: the arithmetic; x and mask are cast to it, P and B must hold it already
+    (split_state(dtype=...)). record: optional dict that receives the branches a
+    forward takes, in relu_masks' layout (see branches)."""
     N, T, V, C = x.shape
+    x, mask = x.to(dtype), mask.to(dtype)
     h = x.permute(0, 2, 3, 1).contiguous().view(N, V * C, T)              # st_gcn_aaai18.py:120-121
     h = _bn(h, P, B, "backbone.data_bn")
     h = h.view(N, V, C, T).permute(0, 2, 3, 1).contiguous().view(N, C, T, V)
@@ -90,10 +97,10 @@ def forward(P: Dict[str, torch.Tensor], B: Dict[str, torch.Tensor], x: torch.Ten
         n, kc, t, v = y.size()
         y = y.view(n, Ae.size(0), kc // Ae.size(0), t, v)
         y = torch.einsum("nkctv,kvw->nctw", (y, Ae)).contiguous()           # gconv_origin.py:64
-        y = _relu(_bn(y, P, B, p + "tcn.0"), ("H", i), relu_masks)
+        y = _relu(_bn(y, P, B, p + "tcn.0"), ("H", i), relu_masks, record)
         y = F.conv2d(y, P[p + "tcn.2.weight"], P[p + "tcn.2.bias"], stride=(s, 1), padding=(1, 0))
         y = _bn(y, P, B, p + "tcn.3")
-        h = _relu(y + res, ("O", i), relu_masks)
+        h = _relu(y + res, ("O", i), relu_masks, record)
         if taps is not None:
             if h.requires_grad:
                 h.retain_grad()
@@ -101,37 +108,55 @@ def forward(P: Dict[str, torch.Tensor], B: Dict[str, torch.Tensor], x: torch.Ten
     feat = h.permute(0, 2, 3, 1).contiguous().view(N, h.size(2), -1)      # st_gcn_aaai18.py:131-132
     bs, w, c = feat.shape
     z = F.linear(feat.view(bs * w, c), P["pose_regressor.0.weight"], P["pose_regressor.0.bias"])
+    if record is not None:
+        record["P"] = (z.detach() > 0).float()
     if relu_masks is None:
         z = F.leaky_relu(z, 0.01)
     else:
-        z = z * (relu_masks["P"] + (1.0 - relu_masks["P"]) * 0.01)
+        pm = relu_masks["P"].to(z.dtype)
+        z = z * (pm + (1.0 - pm) * 0.01)
     z = z * (mask.view(bs * w, -1) / (1.0 - DROPOUT_P))
     z = F.linear(z, P["pose_regressor.3.weight"], P["pose_regressor.3.bias"])
     return z.view(bs, w, -1)
 
 
-def split_state(sd: Dict[str, np.ndarray], layers=IK_LAYERS) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
+def split_state(sd: Dict[str, np.ndarray], layers=IK_LAYERS,
+                dtype=torch.float32) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor]]:
     names = set(param_names(layers))
-    P = {k: torch.tensor(np.asarray(v, np.float32), requires_grad=True) for k, v in sd.items() if k in names}
-    B = {k: torch.tensor(np.asarray(v, np.float32)) for k, v in sd.items()
+    P = {k: torch.tensor(np.asarray(v, np.float32), dtype=dtype, requires_grad=True) for k, v in sd.items()
+         if k in names}
+    B = {k: torch.tensor(np.asarray(v, np.float32), dtype=dtype) for k, v in sd.items()
          if k not in names and not k.endswith("num_batches_tracked")}
     return P, B
 
 
-def train_steps(sd: Dict[str, np.ndarray], batches, lr=1e-4, layers=IK_LAYERS, relu_masks=None):
+def branches(sd: Dict[str, np.ndarray], x, mask, layers=IK_LAYERS, dtype=torch.float32) -> Dict:
+    """The relu_masks dict of a natural forward in `dtype`: the branch every ReLU /
+    LeakyReLU takes on (x, mask), as 0/1 fp32 tensors in forward's layouts."""
+    P, B = split_state(sd, layers, dtype)
+    rec = {}
+    with torch.no_grad():
+        forward(P, B, torch.from_numpy(np.asarray(x, np.float32)), torch.from_numpy(np.asarray(mask, np.float32)),
+                layers, dtype=dtype, record=rec)
+    return rec
+
+
+def train_steps(sd: Dict[str, np.ndarray], batches, lr=1e-4, layers=IK_LAYERS, relu_masks=None,
+                dtype=torch.float32):
     """Run len(batches) optimizer steps; batches = [(x, target, mask)] numpy.
     Returns per-step losses, the first step's gradients, and the final state.
-    relu_masks (one step only): see forward."""
+    relu_masks (one step only): see forward. dtype=torch.float64: parameters,
+    buffers, inputs, masks and targets in float64 (results are float64 arrays)."""
     torch.set_grad_enabled(True)
-    P, B = split_state(sd, layers)
+    P, B = split_state(sd, layers, dtype)
     order = [P[n] for n in param_names(layers)]
     opt = torch.optim.Adam(order, lr=lr)                                   # pose_trainer.py:196-197
     losses, grads0 = [], None
     for x, tgt, mask in batches:
         opt.zero_grad()
         y = forward(P, B, torch.from_numpy(np.asarray(x, np.float32)), torch.from_numpy(np.asarray(mask, np.float32)),
-                    layers, relu_masks=relu_masks)
-        loss = F.mse_loss(y, torch.from_numpy(np.asarray(tgt, np.float32)))   # pose_trainer.py:46-49
+                    layers, relu_masks=relu_masks, dtype=dtype)
+        loss = F.mse_loss(y, torch.from_numpy(np.asarray(tgt, np.float32)).to(dtype))   # pose_trainer.py:46-49
         loss.backward()
         if grads0 is None:
             grads0 = {k: v.grad.detach().numpy().copy() for k, v in P.items()}

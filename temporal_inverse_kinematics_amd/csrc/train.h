@@ -119,8 +119,9 @@ int mse_eval_blocks(long long n);
 hipError_t launch_mse_eval(const float* O, int ldo, const float* T, long long rows, int cols, float* loss, double* part,
                            hipStream_t st);
 // torch.optim.Adam (single-tensor path): m = lerp(m, g, 1-b1); v = v*b2 + (1-b2) g^2;
-// p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
-hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2,
+// p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps). b1, b2, bc1 = 1 - b1^step, bc2 = 1 - b2^step in double;
+// the kernel takes each of 1-b1, b2, 1-b2, -lr/bc1, sqrt(bc2) rounded to fp32 once, as torch's fp32 step does
+hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, double b1, double b2,
                        float eps, double bc1, double bc2, hipStream_t st);
 
 }  // namespace tik

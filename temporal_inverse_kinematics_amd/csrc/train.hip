@@ -875,14 +875,14 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     v[i] = vi;
 }
 
-hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2,
+hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, double b1, double b2,
                        float eps, double bc1, double bc2, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
+    const float w1 = (float)(1.0 - b1), w2 = (float)(1.0 - b2);
     const float step_size = (float)(-(double)lr / bc1);
     const float bc2s = (float)sqrt(bc2);
-    hipLaunchKernelGGL(adam_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, p, g, m, v, n, w1, b2, w2, step_size, bc2s,
-                       eps);
+    hipLaunchKernelGGL(adam_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, p, g, m, v, n, w1, (float)b2, w2, step_size,
+                       bc2s, eps);
     return hipGetLastError();
 }
 

@@ -90,7 +90,11 @@ struct tik_trainer {
     long long perm_blocks = 0;
     std::vector<DevBuf> dbg_dx;   // TIK_TRAIN_DEBUG=1: each block's input gradient of the last step
     DevBuf dbg_b[5];              // TIK_TRAIN_DEBUG_LAYER=l: that block's gS, dU, dH (post-ReLU), dZ, dY
-    float lr = 1e-4f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, momentum = 0.1f;
+    float lr = 1e-4f, eps = 1e-8f, momentum = 0.1f;
+    // Adam's betas in double, as torch.optim.Adam holds them: the bias corrections 1 - beta^steps
+    // and the weights 1 - beta come from these, never from a value already rounded to fp32
+    // (1 - 0.999f is 1.3e-5 off 0.001, which moves sqrt(bc2), and so every update, by 6e-6)
+    double beta1 = 0.9, beta2 = 0.999;
     // eval pass (tik_trainer_eval): the folded eval set is valid for weight version
     // `folded_at`; step() and tik_trainer_write bump `version`
     long long version = 1, folded_at = 0;
@@ -493,8 +497,8 @@ int step(tik_trainer* t, const float* x, int N, int T, const float* target, cons
     if ((rc = bn_back(t, gOut, t->x4.p, R0, 4 * V, t->cmap0.p, t->dg, t->db, t->st0.p, nullptr, st))) return rc;
     // Adam
     t->steps += 1;
-    const double bc1 = 1.0 - std::pow((double)t->beta1, (double)t->steps);
-    const double bc2 = 1.0 - std::pow((double)t->beta2, (double)t->steps);
+    const double bc1 = 1.0 - std::pow(t->beta1, (double)t->steps);
+    const double bc2 = 1.0 - std::pow(t->beta2, (double)t->steps);
     HIP_TRY(tik::launch_adam(P, Gd, t->M.p, t->Vv.p, t->np, t->lr, t->beta1, t->beta2, t->eps, bc1, bc2, st));
     return derive(t, st);
 }

@@ -285,7 +285,7 @@ def fk_family(config, reserve=FK_RESERVE):
 
 
 # ---------------------------------------------------------------- trainer
-TRAIN_STEPS = [(64, 9), (64, 9), (3, 9), (6, 17)]
+TRAIN_STEPS = [(64, 9), (64, 9), (3, 9), (6, 17), (2, 1), (1, 2), (5, 4)]
 TRAIN_EVALS = [(1, 1), (5, 17)]
 
 
@@ -317,8 +317,9 @@ def trainer_state(tr, tag, out):
 
 def trainer_family():
     """Two steps at (64,9), then a smaller batch and another window length
-    (the workspaces keep the larger calls' rows), the whole state after each;
-    then evals at one frame and at (5,17)."""
+    (the workspaces keep the larger calls' rows), then windows below 9 frames
+    ((2,1): every temporal tap in the padding; (1,2), (5,4): the stride-2
+    layers collapse to one frame), the whole state after each; then evals at one frame and at (5,17)."""
     tr = new_trainer()
     out = {}
     for i, (N, T) in enumerate(TRAIN_STEPS):
