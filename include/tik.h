@@ -229,6 +229,10 @@ int tik_train_windows(const float* joints, int n_joints, const float* poses, int
  *
  * tik_trainer_create: the PoseRegressor state dict (as tik_model_create,
  *   incl. "tik.strides"); parameters and buffers are copied to the device.
+ *   Every tensor is checked for rank and for the exact number of values it
+ *   holds: a malformed one (wrong rank, null data, short or long, an empty
+ *   or fractional "tik.strides") is refused by name, TIK_E_INVALID, before
+ *   any device call.
  * tik_trainer_step: x [N][T][17][3], target [N][T'][66] (device fp32);
  *   dropout_mask [N*T'][512] of 0/1 (device), or NULL = a counter-based mask
  *   keyed by `seed`; loss: device float (or NULL). Stream-ordered.
@@ -272,7 +276,8 @@ int tik_trainer_set_steps(tik_trainer_t t, long long steps);
  * (which 0 output, 2 tcn conv output, 3 post-ReLU tcn input, 4 graph-mix
  * output, 5 gcn conv output; 6 the head's first Linear output), and with
  * TIK_TRAIN_DEBUG=1 (TIK_TRAIN_DEBUG_LAYER=l) its input gradient (1) and
- * backward intermediates (10..14); n floats to device dst. */
+ * backward intermediates (10..14); n floats to device dst. Both variables
+ * are read by tik_trainer_create, which refuses a layer outside 0..L-1. */
 int tik_trainer_debug(tik_trainer_t t, int which, int layer, float* dst, long long n, void* stream);
 
 /* ------------------------------------------------------------------------

@@ -59,9 +59,6 @@ hipError_t launch_im2col(float* col, const float* src, int lds, int C, int kt, i
                          int tout, int V, hipStream_t st);
 // up[(n*tin + t)*V + v][c] = t % s == 0 ? src[(n*tout + t/s)*V + v][c] : 0
 hipError_t launch_upsample(float* up, const float* src, int C, int s, int N, int tin, int tout, int V, hipStream_t st);
-// dst[i0*ds0 + i1*ds1 + i2*ds2] = src[soff + i0*ss0 + i1*ss1 + i2*ss2] (weight repacking)
-hipError_t launch_permute(float* dst, const float* src, int d0, int d1, int d2, long long ds0, long long ds1,
-                          long long ds2, long long soff, long long ss0, long long ss1, long long ss2, hipStream_t st);
 // A batch of re-layouts in one launch: dst[i0*ds0 + i1*ds1 + i2*ds2] =
 // src[s] (* src2[s] when src2 != null), s = soff + i0*ss0 + i1*ss1 + i2*ss2.
 struct PermDesc {
@@ -75,8 +72,6 @@ struct PermDesc {
 // assigns block ranges; returns the grid size
 long long permute_batch_blocks(PermDesc* descs, int nd);
 hipError_t launch_permute_batch(const PermDesc* descs_dev, int nd, long long blocks, hipStream_t st);
-// dst = a * b elementwise (n)
-hipError_t launch_mul(float* dst, const float* a, const float* b, int n, hipStream_t st);
 // dropout keep mask (1 with probability keep, else 0) from a counter-based hash of (seed, i)
 hipError_t launch_dropout_mask(float* mask, long long n, float keep, unsigned long long seed, hipStream_t st);
 // D = LeakyReLU(P, 0.01) * mask * scale

@@ -586,27 +586,6 @@ hipError_t launch_upsample(float* up, const float* src, int C, int s, int N, int
     return hipGetLastError();
 }
 
-__global__ void permute_kernel(float* __restrict__ dst, const float* __restrict__ src, int d0, int d1, int d2,
-                               long long ds0, long long ds1, long long ds2, long long soff, long long ss0,
-                               long long ss1, long long ss2) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)d0 * d1 * d2) return;
-    const int i2 = (int)(i % d2);
-    const long long q = i / d2;
-    const int i1 = (int)(q % d1);
-    const int i0 = (int)(q / d1);
-    dst[i0 * ds0 + i1 * ds1 + i2 * ds2] = src[soff + i0 * ss0 + i1 * ss1 + i2 * ss2];
-}
-
-hipError_t launch_permute(float* dst, const float* src, int d0, int d1, int d2, long long ds0, long long ds1,
-                          long long ds2, long long soff, long long ss0, long long ss1, long long ss2, hipStream_t st) {
-    const long long n = (long long)d0 * d1 * d2;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(permute_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, dst, src, d0, d1, d2, ds0, ds1, ds2, soff,
-                       ss0, ss1, ss2);
-    return hipGetLastError();
-}
-
 // every weight re-layout of a step in one launch: workgroup b serves the
 // descriptor whose block range holds b (ranges laid out by the host)
 __global__ __launch_bounds__(256) void permute_batch_kernel(const PermDesc* __restrict__ descs, int nd) {
@@ -638,17 +617,6 @@ long long permute_batch_blocks(PermDesc* descs, int nd) {
 hipError_t launch_permute_batch(const PermDesc* descs_dev, int nd, long long blocks, hipStream_t st) {
     if (nd == 0 || blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(permute_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, st, descs_dev, nd);
-    return hipGetLastError();
-}
-
-__global__ void mul_kernel(float* dst, const float* a, const float* b, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = a[i] * b[i];
-}
-
-hipError_t launch_mul(float* dst, const float* a, const float* b, int n, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(mul_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, dst, a, b, n);
     return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 `GpuTrainer` runs what Lightning does with `IKPoseTrainer` for one batch
 (pose_trainer.py:146-155 `training_step`, the backward, and the Adam step
 from `configure_optimizers`, :196-197) as one stream-ordered call into
-libtik.so (`tik_trainer_step`, csrc/trainer.cpp):
+libtik.so (`tik_trainer_step`, csrc/train_step.cpp; the handle in
+csrc/train_model.cpp, the state dict's validation and layout in csrc/train_plan.h):
 
   * train-mode forward: BatchNorm on batch statistics with the running-stat
     momentum update (st_gcn_aaai18.py:74-75,178,186,203), Dropout(0.7) in the

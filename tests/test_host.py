@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import fk_constants_cases as fk_cases
+import train_plan_cases as plan_cases
 from conftest import REPO, golden
 
 
@@ -112,6 +113,41 @@ def test_fk_create_refuses_malformed_constants_without_gpu(case):
     arr = (_lib.TikTensor * len(items))(*items)
     h = ct.c_void_p(0xdead)
     rc = lib.tik_fk_create(arr, len(items), 1, ct.byref(h))
+    assert rc == _lib.TIK_E_INVALID, (rc, _lib.last_error())
+    assert name in _lib.last_error(), _lib.last_error()
+    assert h.value is None
+
+
+TRAINER_OLD_CASES = ["rank-1 gcn.conv.weight", "backbone.A null data", "short edge_importance.0", "ndim 5",
+                     "rank-1 pose_regressor.0.weight", "63 of 64 running_var"]
+
+
+@pytest.mark.parametrize("case", TRAINER_OLD_CASES + list(plan_cases.CASES))
+def test_trainer_create_refuses_malformed_state_dict_without_gpu(case, ik_weights):
+    """tik_trainer_create takes the same state dict over the same C ABI, and the
+    training kernels read `cout` values at each tensor's recorded offset: a tensor
+    of the wrong rank, with null data, cut short or too long is refused by name on
+    the host (csrc/train_plan.h), before any shape[i] / v[i] is read and before the
+    first device call: with no device, a state dict that got as far as an upload
+    would come back as an allocation failure instead."""
+    from temporal_inverse_kinematics_amd import _lib
+    ct = _lib.ctypes
+    lib = _lib.load()
+    if case in TRAINER_OLD_CASES:
+        tensors, name = _malformed(plan_cases.with_strides(ik_weights), case)
+        tensors = [(k, np.ascontiguousarray(ik_weights.get(k, v) if v is None else v, dtype=np.float32), v is not None, nd)
+                   for k, v, nd in tensors]
+    else:
+        tensors, name = plan_cases.malformed(ik_weights, case)
+        tensors = [(k, a, has, None) for k, a, has in tensors]
+    items, keep = [], []
+    for k, a, has, nd in tensors:
+        keep += [a, k.encode()]
+        items.append(_lib.TikTensor(keep[-1], a.ctypes.data_as(_lib._F) if has else None, a.ndim if nd is None else nd,
+                                    (ct.c_int64 * 4)(*(list(a.shape) + [1] * (4 - a.ndim)))))
+    arr = (_lib.TikTensor * len(items))(*items)
+    h = ct.c_void_p(0xdead)
+    rc = lib.tik_trainer_create(arr, len(items), ct.c_float(1e-4), ct.byref(h))
     assert rc == _lib.TIK_E_INVALID, (rc, _lib.last_error())
     assert name in _lib.last_error(), _lib.last_error()
     assert h.value is None
