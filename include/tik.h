@@ -171,8 +171,12 @@ int tik_moveai_to_coco(const float* joints, int F, int J, const int* map17_host,
  * Flush the last h frames by pushing the last frame h more times.
  * ---------------------------------------------------------------------- */
 /* The stream keeps a reference on `model` (released by tik_stream_destroy)
- * and a private workspace sized for (1, 2h+1): batch calls on the model handle
- * (any size, any stream) do not disturb a live stream. */
+ * and private buffers for the one step it runs (tik_stream_path): batch calls
+ * on the model handle (any size, any stream) do not disturb a live stream.
+ * tik_stream_create refuses (TIK_E_INVALID, before any device call) a
+ * win_size that is not positive or so large that 2 (2h+1) exceeds 2^29, a
+ * backbone-only handle, and a model whose pose width (rows of
+ * pose_regressor.3) is not 66. */
 typedef struct tik_stream* tik_stream_t;
 int tik_stream_create(tik_model_t model, int win_size, int use_graph, tik_stream_t* out);
 int tik_stream_destroy(tik_stream_t s);

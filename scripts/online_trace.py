@@ -32,7 +32,7 @@ def main():
     tr = np.frombuffer(buf, dtype=np.int64).reshape(n, 8).astype(np.float64)
     t0 = tr[:, 0].min()
     us = (tr[:, :7] - t0) / 100.0   # 100 MHz ticks -> us
-    # phase table (stream.cpp setup_online)
+    # phase table, restated for the IK net (csrc/stream_plan.h plan_dataflow is the rule)
     strides = [1, 1, 2, 1, 1, 2, 2, 2]
     couts = [64, 64, 128, 128, 128, 128, 256, 256]
     W = 2 * (a.win // 2) + 1

@@ -16,6 +16,7 @@
 
 #include "../../include/tik.h"
 #include "fold.h"
+#include "online_defs.h"
 
 namespace tik_host {
 
@@ -122,30 +123,6 @@ struct DevArray {   // owning device buffer; move-only (a copy would double-free
 using DevBuf = DevArray<float>;
 using DevIBuf = DevArray<int>;
 using DevHBuf = DevArray<unsigned short>;
-
-// fp32 -> bf16 bits, round to nearest even (finite inputs; NaN stays NaN)
-inline unsigned short bf16_rne(float x) {
-    unsigned u;
-    memcpy(&u, &x, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (unsigned short)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-inline float bf16_to_f32(unsigned short b) {
-    const unsigned u = (unsigned)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-// x = p0 + p1 + p2 with p_i = bf16_rne(x - p0 - ... - p_{i-1}): exact for
-// normal fp32 x (each plane takes the next 8 significant bits, the
-// residuals are exact in fp32), full fp32 exponent range
-inline void split_bf16x3(float x, unsigned short& p0, unsigned short& p1, unsigned short& p2) {
-    p0 = bf16_rne(x);
-    const float r1 = x - bf16_to_f32(p0);
-    p1 = bf16_rne(r1);
-    const float r2 = r1 - bf16_to_f32(p1);
-    p2 = bf16_rne(r2);
-}
 
 // fp32 weights [Nc][kt][cin] (row stride ldw floats) -> three bf16 planes
 // [Nc][kt][cin8] (cin8 = cin rounded up to 8, zero-filled): w = p0 + p1 + p2
@@ -262,19 +239,13 @@ struct ProfRange {
 }  // namespace tik_host
 
 struct tik_model;
-namespace tik { struct OnlineArgs; }
 namespace tik_host {
-// internal entry points shared by model.cpp, forward.cpp and stream.cpp
+// internal entry points shared by model.cpp, forward.cpp and the stream code (stream.h)
 int model_reserve_ws(tik_model* m, Workspace& w, int N, int T);
 // the IK forward on workspace w; split = may run as two halves on two streams
 int model_forward_ws(tik_model* m, const float* x, int N, int T, float* poses, hipStream_t st, Workspace& w,
                      bool split);
 void model_retain(tik_model* m);    // a stream keeps its model alive
 void model_release(tik_model* m);   // deletes the model at the last reference
-// the fp32 weights and shapes of the online-IK dataflow kernel (online.h);
-// TIK_E_INVALID when the model is outside what that kernel supports
-int model_online_fill(tik_model* m, tik::OnlineArgs& a);
-int model_pose_dim(const tik_model* m);   // 0 for a backbone-only handle
-
 
 }  // namespace tik_host

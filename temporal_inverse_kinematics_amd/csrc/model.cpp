@@ -7,7 +7,7 @@
 #include <memory>
 
 #include "model.h"
-#include "online.h"
+#include "stream.h"
 
 using namespace tik_host;
 
@@ -101,32 +101,22 @@ int model_reserve_ws(tik_model* m, Workspace& w, int N, int T) {
 }
 
 void model_retain(tik_model* m) { m->refs.fetch_add(1); }
-int model_pose_dim(const tik_model* m) { return m->pose_dim; }
 void model_release(tik_model* m) {
     if (m->refs.fetch_sub(1) == 1) delete m;
 }
 
-int model_online_fill(tik_model* m, tik::OnlineArgs& a) {
+OnlineModelView model_online_view(const tik_model* m) {
     static_assert((int)tik::ONR_ZERO == RES_ZERO && (int)tik::ONR_IDEN == RES_IDEN && (int)tik::ONR_CONV == RES_CONV, "");
-    const int nl = (int)m->layers.size();
-    if (m->V != 17 || m->C0 != 3 || nl > tik::ONL_MAXL) return fail(TIK_E_INVALID, "online kernel: V=17, 3 input channels, <= %d layers", tik::ONL_MAXL);
-    if (m->pose_dim <= 0) return fail(TIK_E_INVALID, "online kernel: backbone-only handle (no pose_regressor weights)");
-    a.nl = nl;
-    for (int l = 0; l < nl; ++l) {
-        const Layer& L = m->layers[l];
-        if (L.cout % 16 || L.cout > tik::ONL_MAXC || L.cinp > tik::ONL_MAXC || (l > 0 && L.cinp != L.cin))
-            return fail(TIK_E_INVALID, "online kernel: layer %d channels %d -> %d", l, L.cin, L.cout);
-        tik::OnlineLayer& o = a.L[l];
-        o.cin = L.cin; o.cinp = L.cinp; o.cout = L.cout; o.stride = L.stride; o.res = L.res;
-        o.wg = L.wg.p; o.bias2 = L.bias2.p; o.amix = L.amix.p; o.wt = L.wt.p; o.wr = L.wr.p; o.biasT = L.biasT.p;
+    OnlineModelView v;
+    v.shape.V = m->V; v.shape.C0 = m->C0; v.shape.feat = m->feat; v.shape.hidden = m->hidden; v.shape.pose_dim = m->pose_dim;
+    for (const Layer& L : m->layers) {
+        v.shape.layers.push_back({L.cin, L.cinp, L.cout, L.stride, L.res});
+        v.L.push_back({L.wg.p, L.bias2.p, L.amix.p, L.wt.p, L.wr.p, L.biasT.p});
     }
-    if (m->feat % 4 || m->feat > tik::ONL_MAXHC * 256 || m->hidden % 16 || m->hidden > tik::ONL_MAXHC * 256 ||
-        m->pose_dim > 256)   // head tasks: one thread per pose value, W3 columns in LDS
-        return fail(TIK_E_INVALID, "online kernel: head %d -> %d", m->feat, m->hidden);
-    a.w0 = m->w0.p; a.b0 = m->b0.p; a.w3 = m->w3.p; a.b3 = m->b3.p;
-    a.feat = m->feat; a.hidden = m->hidden; a.pose_dim = m->pose_dim;
-    a.bn_sc = m->bn_sc.p; a.bn_sh = m->bn_sh.p;
-    return TIK_OK;
+    v.bn_sc = m->bn_sc.p; v.bn_sh = m->bn_sh.p;
+    v.w0 = m->w0.p; v.b0 = m->b0.p; v.w3 = m->w3.p; v.b3 = m->b3.p;
+    v.ncu = m->ncu;
+    return v;
 }
 }  // namespace tik_host
 

@@ -21,6 +21,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "online_defs.h"
+
 namespace tik {
 
 // The stream's frame count after one more push. It stays below 2^30: past it, a
@@ -33,35 +35,25 @@ __host__ __device__ inline int stream_next_count(int c, int W) {
     return n >= (1 << 30) ? n - 2 * W * ((1 << 29) / (2 * W)) : n;
 }
 
-constexpr int ONL_MAXL = 12;        // layers
-constexpr int ONL_MAXC = 256;       // channels per layer
-constexpr int ONL_MAXHC = 17;       // head K chunks of 4 per lane: K <= 17 * 4 * 64 = 4352 = 17 joints x ONL_MAXC
-enum { ONP_G = 1, ONP_T = 2, ONP_H = 3 };
-enum { ONR_ZERO = 0, ONR_IDEN = 1, ONR_CONV = 2 };
-
 struct OnlineLayer {
-    int cin, cinp, cout, stride, res;
+    int cinp, cout, stride, res;
     int tin;           // the layer's real input frame count (zero padding past it)
-    int n_in, n_out;   // frames computed: z (gcn) / out (temporal conv)
-    const float *wg, *bias2, *amix, *wt, *wr, *biasT;   // the fp32 folded weights of api.cpp's Layer
+    const float *bias2, *amix, *biasT;   // the model's folded fp32 gcn bias, graph mix and temporal conv bias
     int gk32;                    // gcn K = cinp in steps of 32
     const unsigned short* wgp;   // gcn weight planes [cout/16][gk32][3][64][8] (stream-owned)
     const float* wgf;            // gcn weights fp32, [cout][32 gk32] zero-padded (joint 16)
     int k32;                     // temporal conv K = 3 cout (+ cinp, residual conv) in steps of 32
     const unsigned short* wtp;   // its bf16x3 planes [cout/16][k32][3][64 lanes][8] (stream-owned)
     const float* wtf;            // the same weights fp32, [cout][32 k32] zero-padded (joint 16)
+    // n_in frames of z (gcn) and n_out of out (temporal conv) are computed (stream_plan.h)
     const float* x;    // input rows [n_in][17][cinp] (layer 0: built in place from the ring)
     float *z, *out;    // [n_in][17][cout], [n_out][17][cout]
-};
-
-struct OnlinePhase {
-    int kind, layer, nframes, ngroups, task0, cbase;   // cbase: the phase's counter (the head's: tasks done)
 };
 
 struct OnlineArgs {
     int nl, nph, ntasks;
     OnlineLayer L[ONL_MAXL];
-    OnlinePhase ph[2 * ONL_MAXL + 3];
+    OnlinePhase ph[ONL_MAXPH];
     // input: ring of W frames (V*3 floats), count of frames pushed so far
     float* ring;
     int W, h, ra, rb, relative;

@@ -1,0 +1,70 @@
+// stream_step.cpp — the step an online-IK stream records and tik_stream_push.
+// Default step: ONE dataflow kernel (online.hip) that reads the frame from
+// pinned host memory, appends it to the ring, computes only the frames pose
+// row 0 depends on, and writes the pose to pinned host memory. Layered step
+// (TIK_ONLINE=0, or a model that kernel does not cover, stream_plan.h): ring
+// append, window gather, the layered IK forward on the whole window, the pose
+// copy. Either is one hipGraph replay on the private stream when the stream
+// was created with use_graph (stream.cpp).
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstring>
+
+#include "misc.h"
+#include "stream.h"
+
+using namespace tik_host;
+namespace sp = tik_stream_plan;
+
+namespace tik_host {
+
+int stream_record_step(tik_stream* s) {
+    if (s->online) {
+        HIP_TRY(tik::launch_online(s->onl_args.p, s->onl_grid, s->st));
+        return TIK_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(s->frame_in.p, s->host_frame, sizeof(float) * sp::FRAME, hipMemcpyHostToDevice, s->st));
+    HIP_TRY(tik::launch_stream_push(s->ring.p, s->lim.W, sp::FRAME, s->count.p, s->frame_in.p, s->st));
+    HIP_TRY(tik::launch_stream_window(s->ring.p, s->lim.W, sp::V, s->count.p, s->lim.h, sp::ROOT_A, sp::ROOT_B, 1, s->window.p, s->st));
+    int rc = model_forward_ws(s->model, s->window.p, 1, s->lim.W, s->poses.p, s->st, s->ws, false);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(s->host_pose, s->poses.p, sizeof(float) * sp::POSE_DIM, hipMemcpyDeviceToHost, s->st));
+    return TIK_OK;
+}
+
+}  // namespace tik_host
+
+extern "C" int tik_stream_push(tik_stream_t s, const float* frame_host, float* pose_host) {
+    if (!s || !frame_host) return fail(TIK_E_INVALID, "tik_stream_push: bad arguments");
+    memcpy(s->host_frame, frame_host, sizeof(float) * sp::FRAME);
+    if (s->exec) {
+        HIP_TRY(hipGraphLaunch(s->exec, s->st));
+    } else {
+        int rc = stream_record_step(s);
+        if (rc) return rc;
+    }
+    const int next = tik::stream_next_count(s->dcount, s->lim.W);
+    bool seen = false;
+    if (s->online) {
+        // the dataflow kernel's last head task writes the new frame count to pinned
+        // host memory after the pose: spin on it (sooner than the completion signal
+        // hipStreamSynchronize waits for); the stream stays ordered for the next step
+        const auto t0 = std::chrono::steady_clock::now();
+        for (long it = 0;; ++it) {
+            if (*s->host_done == next) { seen = true; break; }
+            if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
+        }
+    }
+    if (!seen) HIP_TRY(hipStreamSynchronize(s->st));
+    ++s->pushed;   // the step appended the frame to the device ring either way
+    s->dcount = next;
+    if (s->online && s->host_pose[sp::POSE_FLAG] != 0.f) {
+        s->host_pose[sp::POSE_FLAG] = 0.f;
+        return fail(TIK_E_HIP, "tik_stream_push: the online kernel timed out waiting on a dependency "
+                               "(this frame's pose is invalid; the stream stays usable)");
+    }
+    const int valid = s->pushed > s->lim.h;   // frame pushed-1-h >= 0 solved
+    if (valid && pose_host) memcpy(pose_host, s->host_pose, sizeof(float) * sp::POSE_DIM);
+    return valid;
+}

@@ -132,8 +132,9 @@ def test_trainer_poisoned_workspace(fill):
 @pytest.mark.parametrize("fill", FILLS)
 @pytest.mark.parametrize("win,online", me.STREAM_CASES)
 def test_stream_poisoned_workspace(win, online, fill):
-    """stream.cpp sets onl_act (tags), onl_cnt, count and ring before the first
-    launch; window, frame_in and poses are written before they are read."""
+    """stream.cpp (alloc_common, alloc_dataflow) sets onl_act (tags), onl_cnt,
+    count and ring before the first launch; the layered step (stream_step.cpp)
+    writes window, frame_in and poses before it reads them."""
     ref = _ref(("stream", win, online), lambda: me.stream_family(win, online))
     with me.poison(fill):
         got = me.stream_family(win, online)
