@@ -1,6 +1,7 @@
 """Config #4: SMPL-X full 55-joint FK + 10475-vertex LBS, batch=4096, 1 GPU.
 
     python bench_fk.py [--batch 4096] [--steps 10] [--warmup 20] [--joints {all,coco}] [--jacobian] [--refine]
+                       [--shape-jacobian] [--fit-shape]
 
 Prints one JSON line: bodies/s, and per kernel (HIP events around every launch
 of a second pass of the same steps, tik_fk_profile) the algorithmic TFLOP/s of
@@ -13,6 +14,10 @@ in this process. --jacobian adds a "jacobian" key (SMPLX.joints_jacobian for
 COCO-17 and the 22 body dofs, per-kernel HIP events against the HBM roof of the
 bytes it must move), --refine a "refine" key (one Levenberg-Marquardt iteration
 of refine.refine_poses: Jacobian, residual map, tik_lm_solve, candidate cost).
+--shape-jacobian adds a "shape_jacobian" key (SMPLX.joints_shape_jacobian for
+COCO-17, measured like --jacobian), --fit-shape a "fit_shape" key (one
+refine.fit_shape of `batch` frames, and tik_lm_accumulate + tik_lm_solve_sum
+alone), both at the same batch.
 """
 import argparse, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -235,6 +240,65 @@ def measure_refine(batch=4096, steps=10, warmup=20):
                      "host-to-device uploads and the copy back; lm_solve: (batch,51,66) systems, output allocated per call"}
 
 
+def measure_shape_jacobian(batch=4096, steps=10, warmup=20):
+    """SMPLX.joints_shape_jacobian(select="coco", return_joints=False) at `batch` bodies
+    on a fresh handle, measured like measure_jacobian: call time, the per-launch
+    profile, and the fk_shape_jacobian launches against the HBM roof of their
+    algorithmic bytes (the (B,51,nb) Jacobian out, the transforms in, the beta
+    workspace written and read)."""
+    import torch
+    from temporal_inverse_kinematics_amd import _build, synthetic as syn
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    _build.build()
+    m = SMPLX(syn.synthetic_smplx_constants(seed=1), batch_size=batch)
+    pose, betas = syn.synthetic_fk_inputs(batch, seed=1)
+    P, Bt = torch.from_numpy(pose).cuda(), torch.from_numpy(betas).cuda()
+    run = lambda: m.joints_shape_jacobian(P, Bt, select="coco", return_joints=False)
+    med, rounds = _timed(run, steps, warmup)
+    k = _profile(m, run, steps)
+    jk = k.get("fk_shape_jacobian", {})
+    roof_ms = None
+    if jk:
+        roof_ms = jk["gbs"] * jk["avg_ms"] / HBM_PEAK_GBS   # bytes / peak bandwidth
+    return {"select": "coco", "num_betas": m.num_betas, "batch": batch, "steps": steps, "warmup": warmup,
+            "shape_jacobian_ms": round(med, 4), "shape_jacobian_ms_rounds": rounds, "workspace_bytes": m.workspace_bytes,
+            "kernels": k, "fk_shape_jacobian_hbm_roof_ms": None if roof_ms is None else round(roof_ms, 4),
+            "fk_shape_jacobian_share_of_hbm_roof": None if not roof_ms else round(roof_ms / jk["avg_ms"], 3),
+            "basis": "median of 5 rounds of `steps` calls between HIP events; kernels: per-launch HIP events "
+                     "(pre-pass and main kernel under one fk_shape_jacobian label); roof = algorithmic bytes / 8 TB/s"}
+
+
+def measure_fit_shape(batch=4096, steps=10, warmup=20):
+    """One refine.fit_shape of `batch` frames (shape Jacobian, residual map,
+    tik_lm_accumulate, tik_lm_solve_sum, the candidate's cost; uploads and the
+    copies back included), and the two tik_lm_* calls alone on (batch,51,nb)."""
+    import numpy as np
+    import torch
+    from temporal_inverse_kinematics_amd import _build, synthetic as syn
+    from temporal_inverse_kinematics_amd.refine import fit_shape
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX, lm_accumulate, lm_solve_sum
+    _build.build()
+    m = SMPLX(syn.synthetic_smplx_constants(seed=1), batch_size=batch)
+    pose, betas = syn.synthetic_fk_inputs(batch, seed=1)
+    th = np.ascontiguousarray(pose[:, :22].reshape(batch, 66))
+    full = torch.zeros((batch, 55, 3), device="cuda")
+    full[:, :22] = torch.from_numpy(pose[:, :22]).cuda()
+    one = torch.from_numpy(np.tile(betas[:1], (batch, 1))).cuda()   # one body shape for the whole sequence
+    kps = m.joints(full, one, select="coco").cpu().numpy()
+    tf, rf = _timed(lambda: fit_shape(th, kps, m), steps, warmup)
+    jac, joints = m.joints_shape_jacobian(full, select="coco")
+    r = joints.reshape(batch, 51).contiguous()
+    partial = lm_accumulate(jac, r)
+    ta, ra = _timed(lambda: lm_accumulate(jac, r, out=partial), steps, warmup)
+    ts, rs = _timed(lambda: lm_solve_sum(partial, mu=1e-3), steps, warmup)
+    return {"batch": batch, "num_betas": m.num_betas, "steps": steps, "warmup": warmup, "fit_shape_ms": round(tf, 4),
+            "lm_accumulate_ms": round(ta, 4), "lm_solve_sum_ms": round(ts, 4), "partial_rows": int(partial.shape[0]),
+            "fit_shape_ms_rounds": rf, "lm_accumulate_ms_rounds": ra, "lm_solve_sum_ms_rounds": rs,
+            "basis": "median of 5 rounds of `steps` calls between HIP events; fit_shape includes its host-to-device "
+                     "uploads, the cost before and after, and the copy back; lm_accumulate: (batch,51,nb) into a "
+                     "preallocated buffer; lm_solve_sum: its rows, output allocated per call"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
@@ -247,6 +311,10 @@ def main():
                     help="also time SMPLX.joints_jacobian (COCO-17, the 22 body dofs)")
     ap.add_argument("--refine", action="store_true",
                     help="also time one Levenberg-Marquardt iteration of refine.refine_poses and tik_lm_solve alone")
+    ap.add_argument("--shape-jacobian", action="store_true",
+                    help="also time SMPLX.joints_shape_jacobian (COCO-17, all betas)")
+    ap.add_argument("--fit-shape", action="store_true",
+                    help="also time one refine.fit_shape and tik_lm_accumulate / tik_lm_solve_sum alone")
     a = ap.parse_args()
     from temporal_inverse_kinematics_amd import synthetic as syn
     out = measure_fk(a.batch, a.steps, a.warmup)
@@ -256,6 +324,10 @@ def main():
         out["jacobian"] = measure_jacobian(a.batch, a.steps, a.warmup)
     if a.refine:
         out["refine"] = measure_refine(a.batch, a.steps, a.warmup)
+    if a.shape_jacobian:
+        out["shape_jacobian"] = measure_shape_jacobian(a.batch, a.steps, a.warmup)
+    if a.fit_shape:
+        out["fit_shape"] = measure_fit_shape(a.batch, a.steps, a.warmup)
     from oracle import smplx_lbs as sl
     c = syn.synthetic_smplx_constants(seed=1)
     pose, betas = syn.synthetic_fk_inputs(16, seed=1)

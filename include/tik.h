@@ -351,14 +351,46 @@ int tik_fk_joints(tik_fk_t fk, const float* full_pose, const float* betas, const
 int tik_fk_joints_jacobian(tik_fk_t fk, const float* full_pose, const float* betas, const float* expression,
                            const float* transl, int B, const int* sel_host, int n_sel, const int* dof_host, int n_dof,
                            float* jac, float* joints, void* stream);
+/* Jacobian of selected joints with respect to the shape, without the mesh:
+ * jac[b][3 s + c][i] = d joint sel[s] component c / d betas[b][i], i < nb =
+ * shapedirs.shape[2]; jac is (B, 3 n_sel, nb) device fp32, row-major. For a
+ * fixed pose the SMPL-X joints are affine in the betas, so this is the exact
+ * difference joints(betas + e_i) - joints(betas), and it is a function of the
+ * pose alone: betas, expression and transl (each may be NULL) are passed on to
+ * tik_fk_joints when joints are asked for and do not change a bit of jac.
+ * sel_host: n_sel (1..256) joint indices as tik_fk_joints_jacobian (NULL is not
+ * allowed): the 55 chain joints, the vertex joints and the static landmarks. A
+ * contour landmark's bin depends on the pose only, so it has a shape Jacobian,
+ * but this call does not read the dynamic tables: an index in that range is
+ * TIK_E_INVALID. joints: (B, n_sel, 3) or NULL; when given it is written by
+ * tik_fk_joints itself (the same bits). With R_k the world rotation of chain
+ * joint k, jd = J_regressor . shapedirs and sd_v = shapedirs[v]:
+ *   chain joint k:  dP_k = dP_parent + R_parent (jd[k] - jd[parent]),  dP_0 = jd[0]
+ *   vertex v:       sum over its skinning entries of W[v][k] (R_k (sd_v - jd[k]) + dP_k)
+ *   landmark:       the barycentric sum of its three vertices
+ * in fp32 FMAs in a fixed order for either tik_fk_set_precision setting (the
+ * skinning entries as tik_fk_joints takes them: the sparse pairs, or all 55
+ * weights under TIK_FK_SKIN=dense): a body's rows are the same bits for any B,
+ * any place in the batch and any selection around a column. The selection
+ * travels in the kernel arguments: a call uploads nothing and is
+ * stream-ordered. Workspace: 1337 + 165 nb floats per body (tik_fk_joints' 1337
+ * + the derivative of the 55 chain joints for every beta; 2987 at nb = 10; plus
+ * one int per body on a handle with face contours); the mesh path's buffers are
+ * never reserved. TIK_E_INVALID: null pointers, B <= 0, n_sel outside 1..256, a
+ * joint index out of range or a contour landmark, a model without betas. */
+int tik_fk_joints_shape_jacobian(tik_fk_t fk, const float* full_pose, const float* betas, const float* expression,
+                                 const float* transl, int B, const int* sel_host, int n_sel,
+                                 float* jac, float* joints, void* stream);
 /* Bytes of device workspace the handle currently owns (constants excluded). */
 long long tik_fk_workspace_bytes(tik_fk_t fk);
 /* Per-launch HIP-event profile of tik_fk_forward (fk_chain, fk_blend, fk_skin,
  * fk_landmarks), tik_fk_joints (fk_chain, fk_joints) and
  * tik_fk_joints_jacobian (fk_chain, fk_jacobian; when joints are asked for,
  * tik_fk_joints' own fk_chain, fk_joints come first and the second fk_chain
- * runs only if no selected joint is made of vertices), as tik_model_profile /
- * _count / _read. */
+ * runs only if no selected joint is made of vertices) and
+ * tik_fk_joints_shape_jacobian (fk_chain, fk_shape_jacobian; with joints
+ * fk_chain, fk_joints, fk_shape_jacobian, the second fk_chain as above), as
+ * tik_model_profile / _count / _read. */
 int tik_fk_profile(tik_fk_t fk, int max_launches);
 int tik_fk_profile_count(tik_fk_t fk);
 int tik_fk_profile_read(tik_fk_t fk, int i, char* label, int label_len, float* ms, double* flops, double* bytes);
@@ -380,6 +412,38 @@ int tik_fk_profile_read(tik_fk_t fk, int i, char* label, int label_len, float* m
  * ---------------------------------------------------------------------- */
 int tik_lm_solve(const float* jac, const float* r, const float* prior, const float* row_w, const float* lambda,
                  float mu, int B, int m, int n, float* delta, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The same least squares with unknowns shared by the whole batch (the shape
+ * step of refine.py): one system
+ *   (sum_b J_b^T W J_b + (mu + lambda) I) delta = -(sum_b J_b^T W r_b + mu prior)
+ * in two calls. Neither takes a handle or owns a workspace; both are
+ * stream-ordered.
+ * tik_lm_accumulate: jac (B,m,n), r (B,m), row_w (m) or NULL (= 1), limits as
+ * tik_lm_solve (1 <= n <= 165, 1 <= m <= 768) -> partial
+ * (ceil(B / TIK_LM_RUN), n (n + 1) / 2 + n) device fp32, allocated by the
+ * caller. Row q holds the lower triangle of sum_b J_b^T W J_b, packed (entry
+ * (i, j <= i) at i (i + 1) / 2 + j), then sum_b J_b^T W r_b, over the bodies
+ * TIK_LM_RUN q .. TIK_LM_RUN q + TIK_LM_RUN - 1 that are below B. One workgroup
+ * per run, everything in LDS; every entry is one fp32 FMA chain from zero,
+ * bodies ascending and rows ascending within a body, so a row's bits depend on
+ * its own bodies only. A sequence longer than one call accumulates each chunk
+ * into its own rows of one buffer (a chunk that is a multiple of TIK_LM_RUN
+ * bodies leaves the rows what one call over the whole sequence writes).
+ * tik_lm_solve_sum: partial (n_part, n (n + 1) / 2 + n), prior (n) or NULL
+ * (= 0), host floats mu >= 0 and lambda >= 0 -> delta (n). One workgroup adds
+ * the n_part rows in ascending order, puts mu + lambda on the diagonal, forms
+ * -(g + mu prior), then factors (Cholesky) and solves exactly as tik_lm_solve
+ * does. mu + lambda > 0 or a full-rank sum is the caller's promise: a pivot
+ * that is not positive writes NaN into delta and nothing else.
+ * TIK_E_INVALID: null jac / r / partial / delta, B <= 0, n_part <= 0, n or m
+ * out of range, mu or lambda negative or NaN.
+ * ---------------------------------------------------------------------- */
+#define TIK_LM_RUN 32   /* bodies per partial sum */
+int tik_lm_accumulate(const float* jac, const float* r, const float* row_w, int B, int m, int n,
+                      float* partial, void* stream);
+int tik_lm_solve_sum(const float* partial, int n_part, const float* prior, float mu, float lambda, int n,
+                     float* delta, void* stream);
 
 #ifdef __cplusplus
 }

@@ -75,6 +75,9 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_fk_joints": (_I, (_P, _P, _P, _P, _P, _I, ctypes.POINTER(_I), _I, _P, _P)),
     "tik_fk_joints_jacobian": (_I, (_P, _P, _P, _P, _P, _I, ctypes.POINTER(_I), _I, ctypes.POINTER(_I), _I, _P, _P, _P)),
     "tik_lm_solve": (_I, (_P, _P, _P, _P, _P, ctypes.c_float, _I, _I, _I, _P, _P)),
+    "tik_fk_joints_shape_jacobian": (_I, (_P, _P, _P, _P, _P, _I, ctypes.POINTER(_I), _I, _P, _P, _P)),
+    "tik_lm_accumulate": (_I, (_P, _P, _P, _I, _I, _I, _P, _P)),
+    "tik_lm_solve_sum": (_I, (_P, _I, _P, ctypes.c_float, ctypes.c_float, _I, _P, _P)),
     "tik_fk_workspace_bytes": (ctypes.c_longlong, (_P,)),
     "tik_fk_profile": (_I, (_P, _I)),
     "tik_fk_profile_count": (_I, (_P,)),

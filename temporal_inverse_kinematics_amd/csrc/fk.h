@@ -123,4 +123,31 @@ struct FkJacArgs {
 };
 hipError_t launch_fk_jacobian(const FkJacArgs& a, hipStream_t st);
 
+// Jacobian of selected joints with respect to the shape (fk_shape.hip), after fk_chain_kernel wrote
+// ajt. For a fixed pose the joints are affine in the betas, so only the world rotations R_k (the 3x3
+// part of A_k in ajt) and constants enter. Two launches:
+//   fk_shape_pre_kernel       per (body, beta i): dP_k,i, the derivative of the 55 posed chain joints,
+//                             joints ascending (a parent comes before its children), into sw
+//   fk_shape_jacobian_kernel  lane = body, wave = output column s; the nb derivatives of joint sel[s],
+//                             stored as three runs of nb floats in the body's rows
+// sw is beta-major so that lane = body reads are coalesced: component c of joint k for beta i of body b
+// at sw[((i * 55 + k) * 3 + c) * B + b].
+constexpr int FKS_MAX_NB = 25;        // nb + ne <= 25 by the 512-wide feature row
+constexpr int FKS_PER_BETA = 55 * 3;  // floats of sw per body and beta (include/tik.h: 1337 + 165 nb)
+struct FkShapeArgs {
+    int B, n_sel, nb, ns, nextra, nz;  // ns = nb + ne: row length of jd; nextra, nz as FkJacArgs
+    const int* parents;      // (55), parents[k] < k
+    const float* jd;         // (55,3,ns)  J_regressor . [shapedirs | exprdirs]
+    const float* ajt;        // (55,B,12)
+    const float* PT;         // [3V][512]: shapedirs[v][c][i] at row 3 v + c, column 486 + i
+    const float* WT;         // [V][64]
+    const int2* nzw;         // (V,nz) or null
+    const int* pick_v;       // as FkJointsArgs
+    const float* pick_w;
+    float* sw;               // (nb, 55, 3, B)
+    float* jac;              // (B, 3 n_sel, nb)
+    unsigned short sel[FKJ_MAX_SEL];
+};
+hipError_t launch_fk_shape_jacobian(const FkShapeArgs& a, hipStream_t st);
+
 }  // namespace tik

@@ -1,5 +1,5 @@
 // fk_forward.cpp — the launch paths of the SMPL-X FK check (include/tik.h:
-// tik_fk_forward, tik_fk_joints, tik_fk_joints_jacobian).
+// tik_fk_forward, tik_fk_joints, tik_fk_joints_jacobian, tik_fk_joints_shape_jacobian).
 // Replaces common/smpl_util.py:22-82 (run_smpl_inference) and the third-party
 // smplx.SMPLX.forward it calls (lbs + landmarks).
 //
@@ -24,8 +24,9 @@
 // order on one stream with each chunk's skinning on the other: 1.01 vs 0.97 ms
 // per 4096 bodies, a lone 2048-body blend takes 0.37 ms and two concurrent
 // ones 0.56; profiles/r06_ab_fk_pipe.txt.)
-// tik_fk_joints / tik_fk_joints_jacobian: the chain into a (B,55,3) workspace,
-// then fk_joints.hip / fk_jacobian.hip on the vertices the selection is made of.
+// tik_fk_joints / tik_fk_joints_jacobian / tik_fk_joints_shape_jacobian: the chain
+// into a (B,55,3) workspace, then fk_joints.hip / fk_jacobian.hip / fk_shape.hip on
+// the vertices the selection is made of.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -320,6 +321,43 @@ int tik_fk_joints_jacobian(tik_fk_t fk, const float* full_pose, const float* bet
                  2.0 * B * (npick * (3.0 * 507 + 12.0 * terms + nd * (4.0 * terms + 27 + 81 + 27)) + 9.0 * n_sel * nd + 150.0 * nd),
                  4.0 * B * (9.0 * n_sel * nd + KP + 12 * NJ + 3 * NJ + 2.0 * tik::FKJAC_PER_DOF * nd), st);
     HIP_TRY(tik::launch_fk_jacobian(k, st));
+    return TIK_OK;
+}
+
+int tik_fk_joints_shape_jacobian(tik_fk_t fk, const float* full_pose, const float* betas, const float* expression,
+                                 const float* transl, int B, const int* sel_host, int n_sel, float* jac, float* joints,
+                                 void* stream) {
+    if (!fk || !full_pose || !sel_host || !jac || B <= 0) return fail(TIK_E_INVALID, "tik_fk_joints_shape_jacobian: bad arguments");
+    if (n_sel < 1 || n_sel > tik::FKJ_MAX_SEL)
+        return fail(TIK_E_INVALID, "tik_fk_joints_shape_jacobian: n_sel must be 1..%d, got %d", tik::FKJ_MAX_SEL, n_sel);
+    if (fk->nb < 1 || fk->nb > tik::FKS_MAX_NB)
+        return fail(TIK_E_INVALID, "tik_fk_joints_shape_jacobian: the model has %d betas, need 1..%d", fk->nb, tik::FKS_MAX_NB);
+    hipStream_t st = (hipStream_t)stream;
+    tik::FkShapeArgs k{};   // the selection travels in the kernel arguments: nothing is uploaded per call
+    int rc, npick;
+    if ((rc = resolve_selection(fk, "tik_fk_joints_shape_jacobian", sel_host, n_sel, true, k.sel, npick))) return rc;
+    // the joints first, on tik_fk_joints itself (its bits, its "fk_chain" / "fk_joints" launches)
+    if (joints && (rc = tik_fk_joints(fk, full_pose, betas, expression, transl, B, sel_host, n_sel, joints, stream))) return rc;
+    // workspace: tik_fk_joints' 1337 floats per body + 165 nb (include/tik.h)
+    if ((rc = reserve_joints_ws(fk, B, true)) || (rc = fk->shpw.reserve((size_t)B * tik::FKS_PER_BETA * fk->nb))) return rc;
+    // the chain with the transforms forced on, unless tik_fk_joints above already ran it that way (it
+    // does when a selected joint is made of vertices)
+    if ((!joints || npick == 0) && (rc = launch_chain_joints(fk, FkInputs{full_pose, betas, expression, transl, B}, true, st)))
+        return rc;
+    k.B = B; k.n_sel = n_sel; k.nb = fk->nb; k.ns = fk->nb + fk->ne; k.nextra = fk->nextra;
+    k.nz = fk->dense ? 0 : fk->sp_nz;
+    k.parents = fk->parents.p; k.jd = fk->jd.p; k.ajt = fk->ajt.p;
+    k.PT = fk->PT.p; k.WT = fk->WT.p; k.nzw = reinterpret_cast<const int2*>(fk->nzw.p);
+    k.pick_v = fk->pick_v.p; k.pick_w = fk->pick_w.p;
+    k.sw = fk->shpw.p; k.jac = jac;
+    // algorithmic, per (body, beta): the chain's 54 rotated differences; per (vertex evaluation,
+    // skinning entry, beta): a 3x3 product, the add of dP and the weighted sum; bytes: the Jacobian
+    // out, A_j in, the beta workspace written and read
+    const double terms = k.nz ? k.nz : NJ, nbd = k.nb;
+    ProfRange pr(fk->profiling ? &fk->prof : nullptr, "fk_shape_jacobian",
+                 2.0 * B * nbd * (54.0 * 12 + npick * terms * 15.0),
+                 4.0 * B * (3.0 * n_sel * nbd + 12 * NJ + 2.0 * tik::FKS_PER_BETA * nbd), st);
+    HIP_TRY(tik::launch_fk_shape_jacobian(k, st));
     return TIK_OK;
 }
 

@@ -96,7 +96,7 @@ int tik_fk_reserve(tik_fk_t fk, int B) {
 long long tik_fk_workspace_bytes(tik_fk_t fk) {
     if (!fk) return fail(TIK_E_INVALID, "null fk handle");
     return (long long)(4 * (fk->feat.n + fk->ablk.n + fk->vposed.n + fk->verts_ws.n + fk->ajt.n + fk->zero_transl.n +
-                            fk->dyn_bin.n + fk->jchain.n + fk->jacw.n) + 2 * fk->trash.n);
+                            fk->dyn_bin.n + fk->jchain.n + fk->jacw.n + fk->shpw.n) + 2 * fk->trash.n);
 }
 
 int tik_fk_profile(tik_fk_t fk, int max_launches) {

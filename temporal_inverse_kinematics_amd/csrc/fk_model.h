@@ -48,6 +48,9 @@ struct tik_fk {
     // workspace: dR and omega of every dof (FKJAC_WS floats per body)
     tik_host::DevArray<unsigned long long> anc;
     tik_host::DevBuf jacw;
+    // tik_fk_joints_shape_jacobian (fk_shape.hip): workspace: d(chain joints) / d(beta) of every beta
+    // (FKS_PER_BETA nb floats per body)
+    tik_host::DevBuf shpw;
     tik_host::Profiler prof;     // per-launch HIP events (tik_fk_profile; bench.py's FK roofline)
     bool profiling = false;
 };

@@ -15,13 +15,11 @@
 // to HBM. A body's arithmetic does not see the batch, so its bits are the same for any B.
 #include "common.h"
 #include "dev_common.h"
+#include "lm_dev.h"
 
+// The accumulation (1.) and the factorisation with its solves (3., 4.) live in lm_dev.h, shared with
+// lm_sum.hip.
 namespace tik {
-
-constexpr int LM_T = 256;     // threads per workgroup
-constexpr int LM_RC = 8;      // rows of J per staged chunk
-constexpr int LM_MAX_N = 165;
-constexpr int LM_MAX_M = 768;
 
 struct LmArgs {
     int B, m, n;
@@ -34,101 +32,29 @@ struct LmArgs {
     float* delta;          // (B,n)
 };
 
-__host__ __device__ constexpr int lm_tri(int i) { return i * (i + 1) / 2; }
-__host__ __device__ constexpr size_t lm_lds_floats(int n) {
-    return (size_t)lm_tri(n) + 2 * (size_t)n + (size_t)LM_RC * n + 2 * LM_RC + 4;
-}
-static_assert(lm_lds_floats(LM_MAX_N) * 4 <= 64 * 1024, "the largest system must fit the workgroup's LDS");
-
 __global__ __launch_bounds__(LM_T) void lm_solve_kernel(LmArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int n = a.n, m = a.m, tid = threadIdx.x, ntri = lm_tri(n);
     const size_t b = blockIdx.x;
-    float* sN = smem;                 // packed lower triangle, then L in place
-    float* sG = sN + ntri;            // J^T W r, then delta
-    float* sY = sG + n;               // y of the forward solve
-    float* sJ = sY + n;               // LM_RC rows of J
-    float* sW = sJ + LM_RC * n;       // their weights
-    float* sR = sW + LM_RC;           // their residuals
-    float* sP = sR + LM_RC;           // [0] pivot, [1] flag (non-zero: not positive definite)
-    for (int e = tid; e < ntri; e += LM_T) sN[e] = 0.f;
-    for (int i = tid; i < n; i += LM_T) sG[i] = 0.f;
-    if (tid == 0) sP[1] = 0.f;
+    const LmLds s(smem, n);
+    for (int e = tid; e < ntri; e += LM_T) s.sN[e] = 0.f;
+    for (int i = tid; i < n; i += LM_T) s.sG[i] = 0.f;
+    if (tid == 0) s.sP[1] = 0.f;
     __syncthreads();
     // 1. normal matrix and gradient, rows ascending
-    const float* J = a.jac + b * m * n;
-    for (int r0 = 0; r0 < m; r0 += LM_RC) {
-        const int rc = min(LM_RC, m - r0);
-        for (int q = tid; q < rc * n; q += LM_T) sJ[q] = J[(size_t)r0 * n + q];
-        if (tid < rc) {
-            sW[tid] = a.row_w ? a.row_w[r0 + tid] : 1.f;
-            sR[tid] = a.r[b * m + r0 + tid];
-        }
-        __syncthreads();
-        for (int e = tid; e < ntri; e += LM_T) {
-            int i = (int)((sqrtf(8.f * (float)e + 1.f) - 1.f) * 0.5f);
-            while (lm_tri(i) > e) --i;
-            while (lm_tri(i + 1) <= e) ++i;
-            const int j = e - lm_tri(i);
-            float acc = sN[e];
-            for (int rr = 0; rr < rc; ++rr) acc = fmaf(sJ[rr * n + i] * sW[rr], sJ[rr * n + j], acc);
-            sN[e] = acc;
-        }
-        for (int i = tid; i < n; i += LM_T) {
-            float acc = sG[i];
-            for (int rr = 0; rr < rc; ++rr) acc = fmaf(sJ[rr * n + i] * sW[rr], sR[rr], acc);
-            sG[i] = acc;
-        }
-        __syncthreads();
-    }
+    lm_accumulate_body(s, a.jac + b * m * n, a.r + b * m, a.row_w, m, n);
     // 2. damping and right-hand side; from here thread i owns row i (n <= 165 < LM_T)
     const int i = tid;
     const bool own = i < n;
-    const int ti = lm_tri(own ? i : 0);
     float x = 0.f;
     if (own) {
-        sN[ti + i] += a.mu + a.lambda[b];
-        x = -(a.prior ? fmaf(a.mu, a.prior[b * n + i], sG[i]) : sG[i]);
+        s.sN[lm_tri(i) + i] += a.mu + a.lambda[b];
+        x = -(a.prior ? fmaf(a.mu, a.prior[b * n + i], s.sG[i]) : s.sG[i]);
     }
     __syncthreads();
-    // 3. Cholesky
-    bool bad = false;
-    for (int j = 0; j < n; ++j) {
-        const int tj = lm_tri(j);
-        float s = 0.f;
-        if (own && i >= j) {
-            s = sN[ti + j];
-            for (int k = 0; k < j; ++k) s = fmaf(-sN[ti + k], sN[tj + k], s);
-            if (i == j) {
-                const bool ok = s > 0.f;
-                if (!ok) sP[1] = 1.f;
-                sP[0] = ok ? sqrtf(s) : 1.f;
-            }
-        }
-        __syncthreads();
-        const float piv = sP[0];
-        bad = sP[1] != 0.f;   // read between the barriers: the same for every thread, and before column j + 1 can set it
-        if (own && i >= j) sN[ti + j] = i == j ? piv : s / piv;
-        __syncthreads();
-        if (bad) break;
-    }
-    if (bad) {
-        if (own) a.delta[b * n + i] = __builtin_nanf("");
-        return;
-    }
-    // 4. L y = rhs, then L^T delta = y
-    for (int j = 0; j < n; ++j) {
-        if (i == j) sY[j] = x / sN[ti + j];
-        __syncthreads();
-        if (own && i > j) x = fmaf(-sN[ti + j], sY[j], x);
-    }
-    if (own) x = sY[i];
-    for (int j = n - 1; j >= 0; --j) {
-        if (i == j) sG[j] = x / sN[ti + j];
-        __syncthreads();
-        if (own && i < j) x = fmaf(-sN[lm_tri(j) + i], sG[j], x);
-    }
-    if (own) a.delta[b * n + i] = sG[i];
+    // 3. Cholesky, 4. L y = rhs, then L^T delta = y
+    const bool ok = lm_factor_solve(s, n, x);
+    if (own) a.delta[b * n + i] = ok ? s.sG[i] : __builtin_nanf("");
 }
 
 }  // namespace tik

@@ -13,13 +13,29 @@ J comes from SMPLX.joints_jacobian (tik_fk_joints_jacobian), the same linear
 map `rel` applied to its rows; the solve is smplx_fk.lm_solve (tik_lm_solve),
 one workgroup per frame. The prior toward the network's pose theta0 is what
 makes the problem well-posed: 17 keypoints do not determine 22 rotations.
+
+The body shape is one set of betas for the whole sequence:
+
+    cost(theta, beta) = sum_f [ 1/2 sum_k w_k |r_fk|^2 + 1/2 prior_weight |theta_f - theta0_f|^2 ]
+                        + 1/2 shape_weight |beta|^2
+
+For fixed poses the joints are affine in beta, so the shape step (fit_shape)
+is one linear least-squares problem shared by all frames, solved exactly:
+
+    (sum_f Jb_f^T W Jb_f + shape_weight I) d = -(sum_f Jb_f^T W r_f + shape_weight beta)
+
+Jb_f comes from SMPLX.joints_shape_jacobian (tik_fk_joints_shape_jacobian)
+with `rel` applied to its rows; the per-frame normal equations are summed by
+smplx_fk.lm_accumulate (tik_lm_accumulate) and solved once by
+smplx_fk.lm_solve_sum (tik_lm_solve_sum). refine_sequence alternates that
+step with refine_poses.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from .smplx_fk import lm_solve
+from .smplx_fk import LM_RUN, lm_accumulate, lm_partial_width, lm_solve, lm_solve_sum
 
 NUM_DOF = 66
 
@@ -51,12 +67,32 @@ def _check_args(poses, seq_3d_kps, iters, prior_weight, joint_weight, lam0):
             raise ValueError("joint_weight must be 17 non-negative values (COCO order)")
 
 
+def _check_prior_poses(prior_poses, F):
+    if prior_poses is not None:
+        q = np.asarray(prior_poses)
+        if q.ndim != 2 or q.shape[0] != F or q.shape[1] < NUM_DOF:
+            raise ValueError(f"prior_poses must be ({F}, >= {NUM_DOF}), got {q.shape}")
+
+
+def _check_shape_args(smplx_model, betas, shape_weight):
+    """The ValueErrors of the shape step, before any device work. -> the number of betas."""
+    if not float(shape_weight) > 0.0:
+        raise ValueError("shape_weight must be > 0: a short or static sequence does not determine 10 shape values, "
+                         "the prior toward the mean shape is what keeps the summed system positive definite")
+    if betas is not None:
+        b = np.asarray(betas)
+        nb = getattr(smplx_model, "num_betas", None)
+        if b.ndim != 1 or b.shape[0] < 1 or (nb is not None and b.shape[0] != nb) or not np.isfinite(b).all():
+            raise ValueError(f"betas must be ({'nb' if nb is None else nb},) finite values, got shape {b.shape}")
+
+
 def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, prior_weight: float = 1e-2,
-                 joint_weight=None, lam0: float = 1e-2) -> dict:
+                 joint_weight=None, lam0: float = 1e-2, prior_poses=None) -> dict:
     """poses (F,66) solved by the IK, seq_3d_kps (F,17,3) COCO -> {"poses": (F,66)
     float32 numpy, "cost": (iters+1, F) host array of the cost per frame}
     (cost[0] is theta0's, each later row the accepted pose's after that
-    iteration; it never increases).
+    iteration; it never increases). prior_poses: None (the prior pulls toward
+    `poses`) or (F,66), the theta0 of the cost when `poses` is a later iterate.
 
     Per frame and iteration: the LM step from the current pose, the candidate's
     cost with SMPLX.joints, accepted where the cost fell (lambda <- lambda / 3),
@@ -65,11 +101,14 @@ def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, pr
     iteration; the cost history is copied once at the end. Frames go through in
     chunks of at most inference.MAX_WINDOWS_PER_CALL."""
     _check_args(poses, seq_3d_kps, iters, prior_weight, joint_weight, lam0)
+    _check_prior_poses(prior_poses, np.asarray(poses).shape[0])
     from .inference import MAX_WINDOWS_PER_CALL
     dev = smplx_model.device
     iters, pw = int(iters), float(prior_weight)
     th_all = torch.as_tensor(np.ascontiguousarray(np.asarray(poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
     F = th_all.shape[0]
+    pr_all = th_all if prior_poses is None else torch.as_tensor(
+        np.ascontiguousarray(np.asarray(prior_poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
     kps_all = torch.as_tensor(np.ascontiguousarray(seq_3d_kps, dtype=np.float32), device=dev).reshape(F, 17, 3)
     wj = None if joint_weight is None else torch.as_tensor(np.asarray(joint_weight, np.float32), device=dev)
     row_w = None if wj is None else wj.repeat_interleave(3).contiguous()
@@ -79,7 +118,7 @@ def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, pr
     with torch.no_grad():
         for s in range(0, F, MAX_WINDOWS_PER_CALL):
             n = min(MAX_WINDOWS_PER_CALL, F - s)
-            th0 = th_all[s:s + n]
+            th0 = pr_all[s:s + n]
             target = _rel(kps_all[s:s + n])
             b = None
             if betas is not None:
@@ -96,7 +135,7 @@ def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, pr
                 data = (sq if wj is None else sq * wj).sum(1)
                 return 0.5 * data + 0.5 * pw * (th - th0).square().sum(1)
 
-            th = th0.clone()
+            th = th_all[s:s + n].clone()
             lam = torch.full((n,), float(lam0), device=dev)
             cost = cost_of((_rel(smplx_model.joints(full_pose(th), b, None, None, select="coco")) - target).reshape(n, 51), th)
             hist[0, s:s + n] = cost
@@ -115,3 +154,109 @@ def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, pr
                 hist[it + 1, s:s + n] = cost
             out[s:s + n] = th
     return {"poses": out.cpu().numpy(), "cost": hist.cpu().numpy()}
+
+
+def _sequence_tensors(poses, seq_3d_kps, joint_weight, dev):
+    th = torch.as_tensor(np.ascontiguousarray(np.asarray(poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
+    F = th.shape[0]
+    kps = torch.as_tensor(np.ascontiguousarray(seq_3d_kps, dtype=np.float32), device=dev).reshape(F, 17, 3)
+    wj = None if joint_weight is None else torch.as_tensor(np.asarray(joint_weight, np.float32), device=dev)
+    return th, kps, wj
+
+
+def _data_term(th, kps, smplx_model, beta, wj):
+    """1/2 sum_f sum_k w_k |r_fk|^2 of the whole sequence at one beta (nb,) device tensor -> 0-d tensor."""
+    from .inference import MAX_WINDOWS_PER_CALL
+    F = th.shape[0]
+    tot = torch.zeros((), device=th.device)
+    for s in range(0, F, MAX_WINDOWS_PER_CALL):
+        n = min(MAX_WINDOWS_PER_CALL, F - s)
+        full = torch.zeros((n, 55, 3), device=th.device)
+        full[:, :22] = th[s:s + n].reshape(n, 22, 3)
+        r = _rel(smplx_model.joints(full, beta[None].expand(n, -1).contiguous(), None, None, select="coco")) - _rel(kps[s:s + n])
+        sq = r.square().sum(2)
+        tot = tot + 0.5 * (sq if wj is None else sq * wj).sum()
+    return tot
+
+
+def fit_shape(poses, seq_3d_kps, smplx_model, betas=None, shape_weight: float = 1e-3, joint_weight=None) -> dict:
+    """poses (F,66), seq_3d_kps (F,17,3) COCO -> {"betas": (nb,) float32 numpy,
+    "cost": (2,) host array}: the betas that minimise, for the given poses,
+    1/2 sum_f sum_k w_k |r_fk|^2 + 1/2 shape_weight |beta|^2, and that cost
+    before and after. One exact step from `betas` (None: zero): the joints are
+    affine in beta, so the minimiser does not depend on where the step starts.
+    Frames go through in chunks of at most inference.MAX_WINDOWS_PER_CALL, each
+    into its own rows of one buffer of partial sums (lm_accumulate), solved
+    once (lm_solve_sum with mu = shape_weight and prior = beta). A step that is
+    NaN is returned as it is; refine_sequence rejects it."""
+    _check_args(poses, seq_3d_kps, 0, 1.0, joint_weight, 1.0)
+    _check_shape_args(smplx_model, betas, shape_weight)
+    from .inference import MAX_WINDOWS_PER_CALL
+    dev = smplx_model.device
+    sw = float(shape_weight)
+    nb = smplx_model.num_betas
+    th, kps, wj = _sequence_tensors(poses, seq_3d_kps, joint_weight, dev)
+    F = th.shape[0]
+    row_w = None if wj is None else wj.repeat_interleave(3).contiguous()
+    beta = torch.zeros((nb,), device=dev) if betas is None else torch.as_tensor(np.asarray(betas, np.float32), device=dev)
+    with torch.no_grad():
+        rows = [(min(MAX_WINDOWS_PER_CALL, F - s) + LM_RUN - 1) // LM_RUN for s in range(0, F, MAX_WINDOWS_PER_CALL)]
+        partial = torch.empty((sum(rows), lm_partial_width(nb)), device=dev)
+        q = 0
+        data0 = torch.zeros((), device=dev)
+        for c, s in enumerate(range(0, F, MAX_WINDOWS_PER_CALL)):
+            n = min(MAX_WINDOWS_PER_CALL, F - s)
+            full = torch.zeros((n, 55, 3), device=dev)
+            full[:, :22] = th[s:s + n].reshape(n, 22, 3)
+            jac, joints = smplx_model.joints_shape_jacobian(full, beta[None].expand(n, -1).contiguous(), None, None, select="coco")
+            r3 = _rel(joints) - _rel(kps[s:s + n])
+            sq = r3.square().sum(2)
+            data0 = data0 + 0.5 * (sq if wj is None else sq * wj).sum()
+            jr = _rel(jac.reshape(n, 17, 3, nb)).reshape(n, 51, nb).contiguous()
+            lm_accumulate(jr, r3.reshape(n, 51).contiguous(), row_weight=row_w, out=partial[q:q + rows[c]])
+            q += rows[c]
+        new = beta + lm_solve_sum(partial, mu=sw, lam=0.0, prior=beta.contiguous(), n=nb)
+        c0 = data0 + 0.5 * sw * beta.square().sum()
+        c1 = _data_term(th, kps, smplx_model, new, wj) + 0.5 * sw * new.square().sum()
+    return {"betas": new.cpu().numpy(), "cost": torch.stack([c0, c1]).cpu().numpy()}
+
+
+def refine_sequence(poses, seq_3d_kps, smplx_model, rounds: int = 3, iters: int = 5, prior_weight: float = 1e-2,
+                    shape_weight: float = 1e-3, joint_weight=None, lam0: float = 1e-2, betas=None) -> dict:
+    """poses (F,66) solved by the IK, seq_3d_kps (F,17,3) COCO -> {"poses": (F,66)
+    float32, "betas": (nb,) float32, "cost": (rounds+1,)}: `rounds` rounds of
+    one shape step (fit_shape) followed by `iters` pose iterations
+    (refine_poses with the round's betas). cost is the total cost of the module
+    docstring, cost[0] that of the inputs; it never increases: new betas are
+    kept only where the total cost fell (a NaN step is rejected), and
+    refine_poses never raises a frame's cost. The pose prior stays anchored at
+    the input poses theta0 through all rounds. betas: the starting shape, None
+    = zero. rounds=0 returns the inputs."""
+    _check_args(poses, seq_3d_kps, iters, prior_weight, joint_weight, lam0)
+    _check_shape_args(smplx_model, betas, shape_weight)
+    if int(rounds) < 0:
+        raise ValueError(f"rounds must be >= 0, got {rounds}")
+    rounds, sw, pw = int(rounds), float(shape_weight), float(prior_weight)
+    nb = smplx_model.num_betas
+    th0 = np.ascontiguousarray(np.asarray(poses, dtype=np.float32)[:, :NUM_DOF])
+    beta = np.zeros(nb, np.float32) if betas is None else np.asarray(betas, np.float32).copy()
+    th = th0.copy()
+
+    def frames(th_np, beta_np, n_it):
+        return refine_poses(th_np, seq_3d_kps, smplx_model, betas=beta_np, iters=n_it, prior_weight=pw,
+                            joint_weight=joint_weight, lam0=lam0, prior_poses=th0)
+
+    def total(per_frame, beta_np):
+        # per frame the data and prior terms as refine_poses itself computes them: its history never
+        # increases, so neither does this sum
+        return float(per_frame.astype(np.float64).sum()) + 0.5 * sw * float(np.square(beta_np.astype(np.float64)).sum())
+
+    cost = [total(frames(th, beta, 0)["cost"][0], beta)]
+    for _ in range(rounds):
+        cand = fit_shape(th, seq_3d_kps, smplx_model, betas=beta, shape_weight=sw, joint_weight=joint_weight)["betas"]
+        if np.isfinite(cand).all() and total(frames(th, cand, 0)["cost"][0], cand) < cost[-1]:
+            beta = cand
+        out = frames(th, beta, iters)
+        th = out["poses"]
+        cost.append(total(out["cost"][-1], beta))
+    return {"poses": th, "betas": beta, "cost": np.asarray(cost)}

@@ -106,6 +106,7 @@ def resolve_select(select, num_joints: int):
 NUM_POSE_JOINTS = 55
 DEFAULT_DOF = tuple(range(22))   # global orient + 21 body joints: the 66 values the IK solves
 LM_MAX_N, LM_MAX_M = 165, 768    # include/tik.h, tik_lm_solve
+LM_RUN = 32                      # include/tik.h, TIK_LM_RUN: bodies per partial sum of tik_lm_accumulate
 
 
 def resolve_dof(dof):
@@ -154,6 +155,74 @@ def lm_solve(jac: torch.Tensor, r: torch.Tensor, lam: torch.Tensor, mu: float = 
     delta = torch.empty((B, n), device=jac.device, dtype=torch.float32)
     _lib.check(_lib.load().tik_lm_solve(jac.data_ptr(), r.data_ptr(), _lib.ptr(prior), _lib.ptr(row_weight),
                                         lam.data_ptr(), mu, B, m, n, delta.data_ptr(), _lib.stream_of(jac)), "lm_solve")
+    return delta
+
+
+def lm_partial_width(n: int) -> int:
+    """Floats of one row of lm_accumulate's output: the packed lower triangle, then the gradient."""
+    return n * (n + 1) // 2 + n
+
+
+def lm_accumulate(jac: torch.Tensor, r: torch.Tensor, row_weight=None, out=None):
+    """Normal equations summed over runs of LM_RUN bodies (tik_lm_accumulate):
+    jac (B,m,n), r (B,m), row_weight (m) non-negative or None (one); contiguous
+    float32 on the device, n <= 165, m <= 768. -> partial (ceil(B / LM_RUN),
+    n (n + 1) / 2 + n): row q the packed lower triangle of sum_b J_b^T W J_b,
+    then sum_b J_b^T W r_b, over bodies LM_RUN q .. LM_RUN q + LM_RUN - 1. out:
+    optional preallocated contiguous float32 tensor of that shape (a slice of
+    the buffer a sequence of several chunks accumulates into)."""
+    if jac.dim() != 3:
+        raise ValueError(f"jac must be (B, m, n), got {tuple(jac.shape)}")
+    B, m, n = (int(s) for s in jac.shape)
+    if B < 1 or not 1 <= n <= LM_MAX_N or not 1 <= m <= LM_MAX_M:
+        raise ValueError(f"lm_accumulate: need B >= 1, 1 <= m <= {LM_MAX_M}, 1 <= n <= {LM_MAX_N}; got {(B, m, n)}")
+    if tuple(r.shape) != (B, m):
+        raise ValueError(f"r must be {(B, m)}, got {tuple(r.shape)}")
+    if row_weight is not None and tuple(row_weight.shape) != (m,):
+        raise ValueError(f"row_weight must be {(m,)}, got {tuple(row_weight.shape)}")
+    for name, t in (("jac", jac), ("r", r), ("row_weight", row_weight)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 tensor")
+    shape = ((B + LM_RUN - 1) // LM_RUN, lm_partial_width(n))
+    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 {shape} tensor")
+    _lib.require_gpu(jac, r, row_weight, out)
+    if out is None:
+        out = torch.empty(shape, device=jac.device, dtype=torch.float32)
+    _lib.check(_lib.load().tik_lm_accumulate(jac.data_ptr(), r.data_ptr(), _lib.ptr(row_weight), B, m, n,
+                                             out.data_ptr(), _lib.stream_of(jac)), "lm_accumulate")
+    return out
+
+
+def lm_solve_sum(partial: torch.Tensor, mu: float = 0.0, lam: float = 0.0, prior=None, n=None):
+    """One damped least-squares step for unknowns shared by the whole batch
+    (tik_lm_solve_sum): (sum_q N_q + (mu + lam) I) delta = -(sum_q g_q + mu prior)
+    over the rows of `partial` (lm_accumulate's output, (n_part, n (n + 1) / 2 + n)),
+    added in ascending order. prior (n) or None (zero); mu >= 0, lam >= 0;
+    mu + lam > 0 or a full-rank sum is the caller's promise (a matrix that is
+    not positive gives an all-NaN delta, nothing else). n: the number of
+    unknowns, or None to take it from the row length. -> delta (n,)."""
+    if partial.dim() != 2 or partial.shape[0] < 1:
+        raise ValueError(f"partial must be (n_part >= 1, n (n + 1) / 2 + n), got {tuple(partial.shape)}")
+    width = int(partial.shape[1])
+    if n is None:
+        n = int(((9 + 8 * width) ** 0.5 - 3) / 2 + 0.5)
+    n = int(n)
+    if not 1 <= n <= LM_MAX_N or lm_partial_width(n) != width:
+        raise ValueError(f"lm_solve_sum: a row of {width} floats is not n (n + 1) / 2 + n for n = {n} in 1..{LM_MAX_N}")
+    if partial.dtype != torch.float32 or not partial.is_contiguous():
+        raise ValueError("partial must be a contiguous float32 tensor")
+    if prior is not None and (tuple(prior.shape) != (n,) or prior.dtype != torch.float32 or not prior.is_contiguous()):
+        raise ValueError(f"prior must be a contiguous float32 {(n,)} tensor, got {tuple(prior.shape)}")
+    mu, lam = float(mu), float(lam)
+    if not mu >= 0.0:
+        raise ValueError(f"mu must be >= 0, got {mu}")
+    if not lam >= 0.0:
+        raise ValueError(f"lam must be >= 0, got {lam}")
+    _lib.require_gpu(partial, prior)
+    delta = torch.empty((n,), device=partial.device, dtype=torch.float32)
+    _lib.check(_lib.load().tik_lm_solve_sum(partial.data_ptr(), int(partial.shape[0]), _lib.ptr(prior), mu, lam, n,
+                                            delta.data_ptr(), _lib.stream_of(partial)), "lm_solve_sum")
     return delta
 
 
@@ -297,6 +366,39 @@ class SMPLX:
         _lib.check(_lib.load().tik_fk_joints_jacobian(self._h, fp.data_ptr(), _lib.ptr(args[0]), _lib.ptr(args[1]),
                                                       _lib.ptr(args[2]), B, csel, n, cdof, k, jac.data_ptr(),
                                                       _lib.ptr(joints), _lib.stream_of(fp)), "SMPLX.joints_jacobian")
+        return jac, joints
+
+    def joints_shape_jacobian(self, full_pose: torch.Tensor, betas=None, expression=None, transl=None, select="coco",
+                              return_joints: bool = True):
+        """full_pose (B,55,3) device -> (jac (B, 3n, num_betas), joints (B,n,3) or None):
+        jac[b, 3s+c, i] = d joint select[s] component c / d betas[b, i]
+        (tik_fk_joints_shape_jacobian, fp32 FMAs for either `precision`). For a
+        fixed pose the joints are affine in the betas, so jac is a function of
+        the pose alone: betas, expression and transl only reach the returned
+        joints. select: "coco" or a sequence of joint indices below
+        num_static_joints (a contour landmark needs the dynamic tables, which
+        this call does not read; None is not allowed). joints, when asked for,
+        are bit for bit those of joints(select=select)."""
+        if select is None:
+            raise ValueError("joints_shape_jacobian needs a selection ('coco' or joint indices); "
+                             "all joints would include the contour landmarks, which are not supported here")
+        sel = resolve_select(select, self.num_joints)
+        for j in sel:
+            if j >= self.num_static_joints:
+                raise ValueError(f"joint {j} is a contour landmark (its vertices are picked by a pose-dependent bin, from "
+                                 f"tables this call does not read); select joints below {self.num_static_joints}")
+        fp = full_pose.reshape(-1, 55, 3).contiguous()
+        B = fp.shape[0]
+        args = [t.contiguous() if t is not None else None for t in (betas, expression, transl)]
+        _lib.require_gpu(fp, *args)
+        n = len(sel)
+        jac = torch.empty((B, 3 * n, self.num_betas), device=fp.device, dtype=torch.float32)
+        joints = torch.empty((B, n, 3), device=fp.device, dtype=torch.float32) if return_joints else None
+        csel = (_lib.ctypes.c_int * n)(*sel)
+        _lib.check(_lib.load().tik_fk_joints_shape_jacobian(self._h, fp.data_ptr(), _lib.ptr(args[0]), _lib.ptr(args[1]),
+                                                            _lib.ptr(args[2]), B, csel, n, jac.data_ptr(),
+                                                            _lib.ptr(joints), _lib.stream_of(fp)),
+                   "SMPLX.joints_shape_jacobian")
         return jac, joints
 
     @property
