@@ -169,6 +169,13 @@ int tik_moveai_to_coco(const float* joints, int F, int J, const int* map17_host,
  * (inference.py:37-67). Returns 1 when a pose was produced (after h+1 pushes),
  * 0 before, <0 on error. The step is one hipGraph replay when use_graph != 0.
  * Flush the last h frames by pushing the last frame h more times.
+ * A frame with a NaN or an Inf in it is refused: tik_stream_push checks the 51
+ * floats on the host before anything is copied or enqueued and returns
+ * TIK_E_INVALID (tik_last_error names the index of the first such value). The
+ * frame is not appended: ring, frame count and the pose of every other frame
+ * are those of a stream that was never offered it. (The dataflow kernel's
+ * ReLUs turn a NaN into 0, so such a frame would otherwise give finite, wrong
+ * poses for every window that holds it.)
  * ---------------------------------------------------------------------- */
 /* The stream keeps a reference on `model` (released by tik_stream_destroy)
  * and private buffers for the one step it runs (tik_stream_path): batch calls

@@ -16,6 +16,7 @@
 // Stands alone in tests/test_stream_plan_host.py.
 #pragma once
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -73,6 +74,30 @@ inline int stream_limits(const ModelShape& m, int win_size, Limits& o) {
     o.ring_floats = (size_t)o.W * FRAME;
     o.poses_floats = (size_t)o.tout * POSE_DIM;
     return TIK_OK;
+}
+
+// ---------------------------------------------------------------- the pushed frame (any step)
+// Index of the first NaN or Inf among n floats, or -1. From the bits, so that no
+// floating-point compile option can fold the test away.
+inline int first_nonfinite(const float* f, int n) {
+    for (int i = 0; i < n; ++i) {
+        unsigned u;
+        memcpy(&u, f + i, sizeof u);
+        if ((u & 0x7f800000u) == 0x7f800000u) return i;
+    }
+    return -1;
+}
+
+// tik_stream_push's check, before anything is copied or enqueued: both ReLUs of the
+// dataflow kernel turn a NaN into 0 (online.hip), so a non-finite frame would give a
+// finite, wrong pose for every window that holds it. It is refused instead.
+inline int check_frame(const float* frame) {
+    const int i = first_nonfinite(frame, FRAME);
+    if (i < 0) return TIK_OK;
+    unsigned u;
+    memcpy(&u, frame + i, sizeof u);
+    return fail(TIK_E_INVALID, "tik_stream_push: frame value %d (joint %d, coordinate %d) is %s; the frame was not appended", i, i / 3, i % 3,
+                (u & 0x007fffffu) ? "NaN" : "infinite");
 }
 
 // ---------------------------------------------------------------- the dataflow step

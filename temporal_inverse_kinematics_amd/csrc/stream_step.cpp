@@ -37,6 +37,8 @@ int stream_record_step(tik_stream* s) {
 
 extern "C" int tik_stream_push(tik_stream_t s, const float* frame_host, float* pose_host) {
     if (!s || !frame_host) return fail(TIK_E_INVALID, "tik_stream_push: bad arguments");
+    // a NaN or Inf is refused here: nothing is copied or enqueued, ring, count and tags stay as they were
+    if (const int rc = sp::check_frame(frame_host)) return rc;
     memcpy(s->host_frame, frame_host, sizeof(float) * sp::FRAME);
     if (s->exec) {
         HIP_TRY(hipGraphLaunch(s->exec, s->st));

@@ -43,6 +43,9 @@ class OnlineIK:
         self._push_fn = lib.tik_stream_push
         self._fbuf = np.zeros(51, np.float32)
         self._fptr = self._fbuf.ctypes.data_as(_lib._F)
+        # a second frame buffer: the one a push filled is kept as the last frame, the other takes the next
+        self._obuf = np.zeros(51, np.float32)
+        self._optr = self._obuf.ctypes.data_as(_lib._F)
         self._pptr = self._pose.ctypes.data_as(_lib._F)
         self.path = "dataflow" if _lib.check(lib.tik_stream_path(self._s)) == 1 else "layered"
 
@@ -58,13 +61,20 @@ class OnlineIK:
         self._last = None
 
     def push(self, frame: np.ndarray) -> Optional[np.ndarray]:
-        """frame (17,3) -> the (66,) pose of the frame h pushes back, or None while filling."""
+        """frame (17,3) -> the (66,) pose of the frame h pushes back, or None while filling.
+        A frame with a NaN or an Inf in it raises ValueError and is not appended: the
+        stream goes on as if it had never been offered."""
         f = np.asarray(frame, dtype=np.float32)
         if f.size != 51:
             raise ValueError("expected one (17,3) COCO frame")
         self._fbuf[:] = f.reshape(-1)
-        self._last = self._fbuf   # the last pushed frame (flush repeats it)
         rc = self._push_fn(self._s, self._fptr, self._pptr)
+        if rc == _lib.TIK_E_INVALID:
+            # a NaN or Inf in the frame: it was not appended (include/tik.h), so flush must not repeat it
+            _lib.check(rc, "OnlineIK.push")
+        # the last frame the ring took (flush repeats it): the two buffers change places, no copy
+        self._last = self._fbuf
+        self._fbuf, self._obuf, self._fptr, self._optr = self._obuf, self._fbuf, self._optr, self._fptr
         if rc < 0:
             _lib.check(rc, "OnlineIK.push")
         return self._pose.copy() if rc == 1 else None

@@ -2,8 +2,8 @@
 header into a stand-alone program and run on the host (CPU only, plain C++17, no
 HIP source): the stream's limits and their refusals, what the dataflow kernel
 covers (a model outside it is a fallback, not an error), the dataflow step's plan
-(frame counts, activation layout, phase table, counter words) and the two weight
-packers.
+(frame counts, activation layout, phase table, counter words), the two weight
+packers, and the check tik_stream_push makes of a frame before it takes it.
 
 Everything is compared exactly: the plan only counts, and the packers only move
 and split values. The rules are restated here in Python and numpy."""
@@ -33,6 +33,7 @@ IK_WINS = (3, 9, 21, 22, 23, 64, 129)
 # pack: argv = pack in out; in: int32 cin cinp cout stride res, float32 wt [cout][3 cout], wr [cout][cinp] (res conv),
 #   wg [cout][cinp]; out: float32 K-concatenated rows, then for the temporal conv and for the gcn: int64 counts of
 #   wf and wp, float32 wf, uint16 wp
+# frame: argv = frame in; in: 51 float32 -> "<code of check_frame> <first_nonfinite> <message>"
 SRC = r'''
 #include <cstdio>
 #include <cstdlib>
@@ -91,8 +92,21 @@ static int pack(int argc, char** argv) {
     fclose(fo);
     return 0;
 }
+static int frame(int argc, char** argv) {
+    FILE* fi = argc == 3 ? fopen(argv[2], "rb") : nullptr;
+    if (!fi) return 2;
+    float f[FRAME + 1];
+    const size_t n = fread(f, sizeof(float), FRAME + 1, fi);
+    fclose(fi);
+    if (n != FRAME) return 2;
+    f[FRAME] = 0.f;
+    const int rc = check_frame(f);
+    printf("%d %d %s\n", rc, first_nonfinite(f, FRAME), rc ? tik_host::g_err.c_str() : "");
+    return 0;
+}
 int main(int argc, char** argv) {
     if (argc >= 2 && !strcmp(argv[1], "plan")) return plan(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "frame")) return frame(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "pack")) return pack(argc, argv);
     return 2;
 }
@@ -344,3 +358,37 @@ def test_packers(program, tmp_path, cin, cout, stride):
                     back[16 * cg + ln % 16, 32 * sk + 8 * (ln // 16):32 * sk + 8 * (ln // 16) + 8] = pl[cg, sk, ln]
         assert np.array_equal(back, want_f.reshape(co, -1))
     assert pos == len(raw)
+
+
+# ---------------------------------------------------------------- the pushed frame
+def run_frame(exe, tmp_path, f):
+    """-> (code, index of the first non-finite value or -1, message)"""
+    fin = str(tmp_path / "frame.in")
+    np.asarray(f, np.float32).tofile(fin)
+    r = subprocess.run([exe, "frame", fin], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    code, idx, msg = r.stdout.rstrip("\n").split(" ", 2)
+    return int(code), int(idx), msg
+
+
+def test_finite_frames_pass(program, tmp_path):
+    """Every finite float32 passes: zeros of both signs, subnormals, the largest values."""
+    tiny, big = np.finfo(np.float32).tiny, np.finfo(np.float32).max
+    f = np.random.default_rng(1).normal(0, 0.3, 51).astype(np.float32)
+    f[:8] = [0.0, -0.0, tiny, -tiny, tiny / 4, np.float32(1e-45), big, -big]
+    assert run_frame(program, tmp_path, f) == (0, -1, "")
+    assert run_frame(program, tmp_path, np.zeros(51)) == (0, -1, "")
+
+
+@pytest.mark.parametrize("where", [0, 1, 32, 50])
+@pytest.mark.parametrize("name,bits", [("NaN", 0x7fc00000), ("NaN", 0xffc00001), ("NaN", 0x7f800001), ("infinite", 0x7f800000),
+                                       ("infinite", 0xff800000)])
+def test_non_finite_frames_are_refused(program, tmp_path, where, name, bits):
+    """Quiet, negative and signalling NaNs and both infinities, at the first, an inner
+    and the last of the 51 values: TIK_E_INVALID, naming the first of them."""
+    f = np.random.default_rng(2).normal(0, 0.3, 51).astype(np.float32)
+    f.view(np.uint32)[where] = bits
+    f.view(np.uint32)[50] = bits if where == 50 else 0x7fc00000     # a later one does not change the answer
+    code, idx, msg = run_frame(program, tmp_path, f)
+    assert (code, idx) == (TIK_E_INVALID, where)
+    assert msg == f"tik_stream_push: frame value {where} (joint {where // 3}, coordinate {where % 3}) is {name}; the frame was not appended"
