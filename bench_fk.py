@@ -1,7 +1,7 @@
 """Config #4: SMPL-X full 55-joint FK + 10475-vertex LBS, batch=4096, 1 GPU.
 
     python bench_fk.py [--batch 4096] [--steps 10] [--warmup 20] [--joints {all,coco}] [--jacobian] [--refine]
-                       [--shape-jacobian] [--fit-shape]
+                       [--shape-jacobian] [--fit-shape] [--smooth]
 
 Prints one JSON line: bodies/s, and per kernel (HIP events around every launch
 of a second pass of the same steps, tik_fk_profile) the algorithmic TFLOP/s of
@@ -17,7 +17,10 @@ of refine.refine_poses: Jacobian, residual map, tik_lm_solve, candidate cost).
 --shape-jacobian adds a "shape_jacobian" key (SMPLX.joints_shape_jacobian for
 COCO-17, measured like --jacobian), --fit-shape a "fit_shape" key (one
 refine.fit_shape of `batch` frames, and tik_lm_accumulate + tik_lm_solve_sum
-alone), both at the same batch.
+alone), both at the same batch. --smooth adds a "smooth" key: tik_lm_solve_chain
+at (m,n) = (51,66) for one sequence of 256 and of 4096 frames and for 64
+sequences of 64 frames, the per-frame tik_lm_solve at the same frame counts, and
+one iteration of refine.refine_smooth.
 """
 import argparse, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -299,6 +302,53 @@ def measure_fit_shape(batch=4096, steps=10, warmup=20):
                      "preallocated buffer; lm_solve_sum: its rows, output allocated per call"}
 
 
+def measure_smooth(steps=10, warmup=20):
+    """smplx_fk.lm_solve_chain on random (F,51,66) systems (workspace preallocated,
+    seq_starts resident): one sequence of F = 256 and of F = 4096 frames (the sweep
+    is sequential in F: one workgroup), 64 sequences of 64 frames, each beside the
+    per-frame lm_solve of the same frames; and one iteration of refine.refine_smooth
+    at F = 4096 in 64 sequences (iters=1 minus iters=0, as measure_refine)."""
+    import numpy as np
+    import torch
+    from temporal_inverse_kinematics_amd import _build, synthetic as syn
+    from temporal_inverse_kinematics_amd.refine import refine_smooth
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX, lm_chain_workspace_floats, lm_solve, lm_solve_chain
+    _build.build()
+    m, n, smooth, mu = 51, 66, 0.1, 1e-2
+    out = {"m": m, "n": n, "smooth": smooth, "steps": steps, "warmup": warmup, "cases": {}}
+    g = torch.Generator(device="cuda").manual_seed(1)
+    for name, F, S in (("1x256", 256, 1), ("1x4096", 4096, 1), ("64x64", 4096, 64)):
+        J = torch.randn((F, m, n), device="cuda", generator=g)
+        r = torch.randn((F, m), device="cuda", generator=g)
+        th = torch.randn((F, n), device="cuda", generator=g)
+        lam = torch.full((S,), 1e-2, device="cuda")
+        lam_f = torch.full((F,), 1e-2, device="cuda")
+        starts = torch.arange(0, F + 1, F // S, device="cuda", dtype=torch.int32)
+        work = torch.empty((lm_chain_workspace_floats(F, n),), device="cuda")
+        w = min(warmup, 3)   # a 4096-frame sweep takes long enough to settle the clocks in a few calls
+        tc, rc = _timed(lambda: lm_solve_chain(J, r, lam, th, smooth, mu=mu, seq_starts=starts, workspace=work), steps, w)
+        tf, rf = _timed(lambda: lm_solve(J, r, lam_f, mu=mu), steps, w)
+        d = lm_solve_chain(J, r, lam, th, smooth, mu=mu, seq_starts=starts, workspace=work)
+        out["cases"][name] = {"frames": F, "sequences": S, "lm_solve_chain_ms": round(tc, 4), "lm_solve_ms": round(tf, 4),
+                              "ratio": round(tc / tf, 2), "us_per_frame_of_a_sequence": round(1e3 * tc / (F // S), 3),
+                              "finite": bool(torch.isfinite(d).all()), "lm_solve_chain_ms_rounds": rc, "lm_solve_ms_rounds": rf}
+    F, S = 4096, 64
+    model = SMPLX(syn.synthetic_smplx_constants(seed=1), batch_size=F)
+    pose, _ = syn.synthetic_fk_inputs(F, seed=1)
+    th0 = np.ascontiguousarray(pose[:, :22].reshape(F, 66))
+    full = torch.zeros((F, 55, 3), device="cuda")
+    full[:, :22] = torch.from_numpy(pose[:, :22]).cuda() + 0.05
+    kps = model.joints(full, select="coco").cpu().numpy()
+    st = np.arange(0, F + 1, F // S)
+    t1, r1 = _timed(lambda: refine_smooth(th0, kps, model, smooth, iters=1, seq_starts=st), steps, min(warmup, 3))
+    t0, r0 = _timed(lambda: refine_smooth(th0, kps, model, smooth, iters=0, seq_starts=st), steps, min(warmup, 3))
+    out["refine_smooth"] = {"frames": F, "sequences": S, "iteration_ms": round(t1 - t0, 4), "iters1_ms": round(t1, 4),
+                            "iters0_ms": round(t0, 4), "iters1_ms_rounds": r1, "iters0_ms_rounds": r0}
+    out["basis"] = ("median of 5 rounds of `steps` calls between HIP events; lm_solve_chain: both launches, workspace and "
+                    "seq_starts resident, delta allocated per call; refine_smooth includes its uploads and the copy back")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
@@ -315,6 +365,9 @@ def main():
                     help="also time SMPLX.joints_shape_jacobian (COCO-17, all betas)")
     ap.add_argument("--fit-shape", action="store_true",
                     help="also time one refine.fit_shape and tik_lm_accumulate / tik_lm_solve_sum alone")
+    ap.add_argument("--smooth", action="store_true",
+                    help="also time tik_lm_solve_chain (1 x 256, 1 x 4096 and 64 x 64 frames) beside tik_lm_solve, and one "
+                         "refine.refine_smooth iteration")
     a = ap.parse_args()
     from temporal_inverse_kinematics_amd import synthetic as syn
     out = measure_fk(a.batch, a.steps, a.warmup)
@@ -328,6 +381,8 @@ def main():
         out["shape_jacobian"] = measure_shape_jacobian(a.batch, a.steps, a.warmup)
     if a.fit_shape:
         out["fit_shape"] = measure_fit_shape(a.batch, a.steps, a.warmup)
+    if a.smooth:
+        out["smooth"] = measure_smooth(a.steps, a.warmup)
     from oracle import smplx_lbs as sl
     c = syn.synthetic_smplx_constants(seed=1)
     pose, betas = syn.synthetic_fk_inputs(16, seed=1)

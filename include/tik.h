@@ -19,6 +19,7 @@
 #ifndef TIK_H
 #define TIK_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -451,6 +452,50 @@ int tik_lm_accumulate(const float* jac, const float* r, const float* row_w, int 
                       float* partial, void* stream);
 int tik_lm_solve_sum(const float* partial, int n_part, const float* prior, float mu, float lambda, int n,
                      float* delta, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The same least squares with neighbouring frames tied together (the
+ * temporally smooth refinement of refine.py): F frames in S sequences,
+ * sequence q the frames a = seq_starts[q] .. b - 1 = seq_starts[q + 1] - 1,
+ * c_f the number of neighbours of f inside its sequence (0, 1 or 2):
+ *   D_f = J_f^T W_f J_f + ((mu + lambda[q]) + smooth c_f) I
+ *   b_f = -( fma(mu, prior_f, J_f^T W_f r_f) + smooth (c_f theta_f - theta_{f-1} - theta_{f+1}) )
+ *   D_f delta_f - smooth delta_{f-1} - smooth delta_{f+1} = b_f
+ * (neighbours inside the sequence only): the Gauss-Newton system of the cost
+ * with 1/2 smooth sum_f |theta_{f+1} - theta_f|^2 added, symmetric positive
+ * definite and block tridiagonal with off-diagonal blocks -smooth I.
+ * jac (F,m,n), r (F,m), prior (F,n) or NULL (= 0), theta (F,n) (NULL allowed
+ * only when smooth == 0), row_w NULL (= 1), (m) with row_w_stride == 0 or
+ * (F,m) with row_w_stride == m, lambda (S), delta (F,n): device fp32;
+ * seq_starts: device int32, S + 1 entries. 1 <= n <= TIK_LM_CHAIN_MAX_N,
+ * 1 <= m <= 768, 1 <= S <= F, mu >= 0, smooth >= 0. No handle; workspace:
+ * tik_lm_chain_workspace_floats(F, n) = F (n (n + 1) / 2 + n) device floats
+ * owned by the caller. Stream-ordered, no host copy. Two launches:
+ * 1. one workgroup per frame writes the packed lower triangle of D_f, then
+ *    b_f, into workspace row f (the accumulation of tik_lm_solve);
+ * 2. one workgroup per sequence, everything in LDS, block Cholesky: frames
+ *    ascending S_f = D_f - smooth^2 S_{f-1}^-1 (S_a = D_a), y_f = b_f + smooth
+ *    x_{f-1}, S_f = L_f L_f^T, x_f = S_f^-1 y_f, S_f^-1 = (L_f^-1)^T L_f^-1;
+ *    L_f and x_f replace workspace row f; frames descending delta_{b-1} =
+ *    x_{b-1}, delta_f = x_f + smooth (L_f L_f^T)^-1 delta_{f+1}.
+ * Every sum is an fp32 FMA chain in a fixed order: a sequence's bits do not
+ * depend on what else is in the launch, and with smooth == 0, or for a
+ * sequence of one frame, delta is bit for bit tik_lm_solve's. A pivot that is
+ * not positive (or NaN) at any frame writes NaN into that whole sequence's
+ * delta and nothing else. A sequence whose bounds are not 0 <= a < b <= F
+ * does no work; no index leaves [0, F) whatever seq_starts holds. That
+ * seq_starts starts at 0, ascends strictly and ends at F is the caller's
+ * promise (smplx_fk.lm_chain_starts checks it on the host).
+ * TIK_E_INVALID: null jac / r / lambda / seq_starts / workspace / delta, null
+ * theta with smooth > 0, F <= 0, S <= 0, S > F, n or m out of range, mu or
+ * smooth negative or NaN, row_w_stride not 0 or m.
+ * ---------------------------------------------------------------------- */
+#define TIK_LM_CHAIN_MAX_N 96
+size_t tik_lm_chain_workspace_floats(int F, int n);
+int tik_lm_solve_chain(const float* jac, const float* r, const float* prior, const float* theta,
+                       const float* row_w, int row_w_stride, const float* lambda, const int* seq_starts,
+                       float mu, float smooth, int F, int S, int m, int n,
+                       float* workspace, float* delta, void* stream);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,8 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_fk_joints_shape_jacobian": (_I, (_P, _P, _P, _P, _P, _I, ctypes.POINTER(_I), _I, _P, _P, _P)),
     "tik_lm_accumulate": (_I, (_P, _P, _P, _I, _I, _I, _P, _P)),
     "tik_lm_solve_sum": (_I, (_P, _I, _P, ctypes.c_float, ctypes.c_float, _I, _P, _P)),
+    "tik_lm_chain_workspace_floats": (ctypes.c_size_t, (_I, _I)),
+    "tik_lm_solve_chain": (_I, (_P, _P, _P, _P, _P, _I, _P, _P, ctypes.c_float, ctypes.c_float, _I, _I, _I, _I, _P, _P, _P)),
     "tik_fk_workspace_bytes": (ctypes.c_longlong, (_P,)),
     "tik_fk_profile": (_I, (_P, _I)),
     "tik_fk_profile_count": (_I, (_P,)),

@@ -7,7 +7,7 @@ reference, each window's output frame 0 is the solution for frame idx
 CLI (README.md:24-26):
     python -m temporal_inverse_kinematics_amd.inference <moveai_3d.npz> [SMPLX_DIR]
         [--ckpt model.ckpt] [--win-size 64] [--out poses.npy] [--check] [--refine N]
-        [--fit-shape R]
+        [--fit-shape R] [--smooth W]
 Without --ckpt the seeded synthetic weights are used (the trained checkpoint
 is not distributed with the reference: .MISSING_LARGE_BLOBS:2).
 """
@@ -81,7 +81,7 @@ def fk_check(poses, seq_3d_kps, smplx_model, betas=None) -> dict:
 
 
 def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = None, win_size: int = 64,
-             device="cuda", check: bool = False, refine: int = 0, fit_shape: int = 0):
+             device="cuda", check: bool = False, refine: int = 0, fit_shape: int = 0, smooth: float = 0.0):
     """inference.run_test:110-145: moveai npz -> COCO -> IK -> (optional) SMPL-X FK.
     check=True (with an SMPL-X dir): the result gains "fk_check" (fk_check above).
     refine=N > 0 (with an SMPL-X dir): N Levenberg-Marquardt iterations on the
@@ -90,13 +90,22 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
     fit_shape=R > 0 (with an SMPL-X dir and refine=N > 0): R rounds of one shape
     step and N pose iterations (refine.refine_sequence); the result gains
     "betas", "poses_refined" comes from those rounds and "fk_check_refined" is
-    taken with those betas. fit_shape=0 leaves every output as it is."""
+    taken with those betas. fit_shape=0 leaves every output as it is.
+    smooth=W > 0 (with an SMPL-X dir and refine=N > 0): the pose iterations tie
+    neighbouring frames with 1/2 W sum_f |theta_{f+1} - theta_f|^2
+    (refine.refine_smooth, the track one sequence), alone or inside the rounds
+    of fit_shape; the output keys are those of refine. smooth=0 leaves every
+    output as it is."""
     if refine < 0:
         raise ValueError(f"refine must be >= 0, got {refine}")
     if fit_shape < 0:
         raise ValueError(f"fit_shape must be >= 0, got {fit_shape}")
     if fit_shape and not (smplx_dir and refine > 0):
         raise ValueError("fit_shape needs an SMPL-X dir (or 'synthetic') and refine=N > 0, the pose iterations per round")
+    if not smooth >= 0:
+        raise ValueError(f"smooth must be >= 0, got {smooth}")
+    if smooth and not (smplx_dir and refine > 0):
+        raise ValueError("smooth needs an SMPL-X dir (or 'synthetic') and refine=N > 0, the pose iterations it smooths")
     if refine and not smplx_dir:
         raise ValueError("refine needs an SMPL-X dir (or 'synthetic'): the refinement runs the FK")
     d = np.load(npz_path, allow_pickle=False)
@@ -122,14 +131,18 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
             result["fk_check"] = fk_check(poses, result["coco"], models["male"])
         if refine and fit_shape:
             from .refine import refine_sequence
-            seq_fit = refine_sequence(poses, result["coco"], models["male"], rounds=fit_shape, iters=refine)
+            seq_fit = refine_sequence(poses, result["coco"], models["male"], rounds=fit_shape, iters=refine,
+                                      smooth_weight=smooth)
             result.update(poses_refined=seq_fit["poses"], betas=seq_fit["betas"])
             if check:
                 result["fk_check_refined"] = fk_check(result["poses_refined"], result["coco"], models["male"],
                                                       betas=result["betas"])
         elif refine:
-            from .refine import refine_poses
-            result["poses_refined"] = refine_poses(poses, result["coco"], models["male"], iters=refine)["poses"]
+            from .refine import refine_poses, refine_smooth
+            if smooth:
+                result["poses_refined"] = refine_smooth(poses, result["coco"], models["male"], smooth, iters=refine)["poses"]
+            else:
+                result["poses_refined"] = refine_poses(poses, result["coco"], models["male"], iters=refine)["poses"]
             if check:
                 result["fk_check_refined"] = fk_check(result["poses_refined"], result["coco"], models["male"])
     return result
@@ -150,6 +163,9 @@ def build_parser():
     p.add_argument("--fit-shape", type=int, default=0, metavar="R",
                    help="with SMPLX_DIR and --refine N: R rounds of one body-shape solve shared by all frames followed "
                         "by N pose iterations (--out X.npy then also saves the betas to X.betas.npy)")
+    p.add_argument("--smooth", type=float, default=0.0, metavar="W",
+                   help="with SMPLX_DIR and --refine N: the pose iterations tie neighbouring frames with the weight W on "
+                        "the squared difference of their poses (one block-tridiagonal solve for the whole track)")
     return p
 
 
@@ -165,7 +181,10 @@ def main(argv=None):
         p.error("--refine N needs N >= 0 and an SMPLX_DIR")
     if a.fit_shape < 0 or (a.fit_shape and not (a.smplx_dir and a.refine > 0)):
         p.error("--fit-shape R needs R >= 0, an SMPLX_DIR and --refine N with N > 0 (the pose iterations per round)")
-    r = run_test(a.npz, a.smplx_dir, a.ckpt, a.win_size, check=a.check, refine=a.refine, fit_shape=a.fit_shape)
+    if not a.smooth >= 0 or (a.smooth and not (a.smplx_dir and a.refine > 0)):
+        p.error("--smooth W needs W >= 0, an SMPLX_DIR and --refine N with N > 0 (the pose iterations it smooths)")
+    r = run_test(a.npz, a.smplx_dir, a.ckpt, a.win_size, check=a.check, refine=a.refine, fit_shape=a.fit_shape,
+                 smooth=a.smooth)
     if a.out:
         np.save(a.out, r.get("poses_refined", r["poses"]))
         if "betas" in r:
@@ -174,7 +193,8 @@ def main(argv=None):
     if "fk_check" in r:
         print(f"FK check: mean root-relative joint distance {r['fk_check']['mean']:.6f}")
     if "poses_refined" in r:
-        print(f"refined {r['poses_refined'].shape[0]} frames with {a.refine} LM iterations")
+        print(f"refined {r['poses_refined'].shape[0]} frames with {a.refine} LM iterations"
+              + (f", smoothness weight {a.smooth:g}" if a.smooth else ""))
     if "betas" in r:
         print(f"fitted {r['betas'].shape[0]} betas in {a.fit_shape} rounds: {np.array2string(r['betas'], precision=3)}")
     if "fk_check_refined" in r:

@@ -29,6 +29,17 @@ with `rel` applied to its rows; the per-frame normal equations are summed by
 smplx_fk.lm_accumulate (tik_lm_accumulate) and solved once by
 smplx_fk.lm_solve_sum (tik_lm_solve_sum). refine_sequence alternates that
 step with refine_poses.
+
+refine_poses treats every frame alone. refine_smooth ties the frames of a
+sequence together:
+
+    cost = sum_f cost(theta_f) + 1/2 smooth_weight sum_f |theta_{f+1} - theta_f|^2
+
+Its Gauss-Newton matrix is block tridiagonal, the diagonal blocks those of
+refine_poses plus smooth_weight c_f I (c_f neighbours), every off-diagonal
+block -smooth_weight I; smplx_fk.lm_solve_chain (tik_lm_solve_chain) solves a
+whole sequence in one workgroup. Weights per frame and keypoint let a keypoint,
+or a whole frame, that was not detected be filled from the neighbours.
 """
 from __future__ import annotations
 
@@ -156,6 +167,145 @@ def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, pr
     return {"poses": out.cpu().numpy(), "cost": hist.cpu().numpy()}
 
 
+def _frame_weights(joint_weight, seq_3d_kps, F):
+    """joint_weight None, (17,) or (F,17) and keypoints (F,17,3) that may hold non-finite values ->
+    (weights (F,17) float32, or None where every weight is one; keypoints float32 with the missing ones
+    zeroed). ValueError on a bad shape or a negative weight. Host only."""
+    kps = np.array(seq_3d_kps, dtype=np.float32).reshape(F, 17, 3)
+    w = None
+    if joint_weight is not None:
+        w = np.asarray(joint_weight, np.float32)
+        if w.shape not in ((17,), (F, 17)) or not (w >= 0).all():
+            raise ValueError(f"joint_weight must be (17,) or ({F}, 17) non-negative values (COCO order), "
+                             f"got shape {w.shape}")
+    seen = np.isfinite(kps).all(2)
+    if not seen.all():
+        w = np.ones((F, 17), np.float32) if w is None else np.broadcast_to(w, (F, 17)).copy()
+        w[~seen] = 0.0
+        w[~(seen[:, 11] & seen[:, 12])] = 0.0    # rel() needs both hips: without them the frame is missing
+        kps[~seen] = 0.0
+    elif w is not None:
+        w = np.broadcast_to(w, (F, 17)).copy()
+    return w, kps
+
+
+def refine_smooth(poses, seq_3d_kps, smplx_model, smooth_weight, betas=None, iters: int = 10,
+                  prior_weight: float = 1e-2, joint_weight=None, lam0: float = 1e-2, prior_poses=None,
+                  seq_starts=None) -> dict:
+    """refine_poses with neighbouring frames tied together: poses (F,66) solved by
+    the IK, seq_3d_kps (F,17,3) COCO -> {"poses": (F,66) float32 numpy, "cost":
+    (iters+1, S) host array of the cost per sequence}. seq_starts: None (one
+    sequence) or S+1 frame indices (smplx_fk.lm_chain_starts). Per sequence
+
+        cost = sum_f [ 1/2 sum_k w_fk |r_fk|^2 + 1/2 prior_weight |theta_f - theta0_f|^2 ]
+               + 1/2 smooth_weight sum_f |theta_{f+1} - theta_f|^2
+
+    the first sum refine_poses's cost, the second over the neighbours inside
+    the sequence. The smoothness is on the axis-angle values themselves: it
+    assumes consecutive frames are far from the +-pi wrap of a rotation vector,
+    which holds for the network's output. smooth_weight > 0 has no default:
+    nobody has measured a good one on real data, the caller chooses.
+
+    joint_weight: None, (17,) or (F,17) non-negative, so a frame's undetected
+    keypoints can be switched off. A non-finite keypoint counts as missing: its
+    weight becomes 0 and its coordinates are zeroed before the upload. A frame
+    whose COCO 11 or 12 is non-finite is missing entirely (rel needs both
+    hips): all its 17 weights become 0, its pose comes from the neighbours and
+    the prior.
+
+    Per iteration: the FK Jacobians in chunks of inference.MAX_WINDOWS_PER_CALL
+    into one (F,51,66) buffer, one smplx_fk.lm_solve_chain call (block
+    tridiagonal, one workgroup per sequence), the candidate's cost with
+    SMPLX.joints, accepted per sequence where its cost fell (lambda <- lambda /
+    3), the old poses kept elsewhere (lambda <- 3 lambda); a NaN step counts as
+    rejected. One lambda per sequence. The sums per sequence are taken over a
+    padded (S, longest) gather, so a sequence's cost, and with it its poses,
+    do not depend on the other sequences. All on the device, no host round
+    trip inside an iteration; cost never increases."""
+    sw = float(smooth_weight)
+    if not sw > 0.0:
+        raise ValueError(f"smooth_weight must be > 0, got {smooth_weight}: refine_poses is the refinement "
+                         "without the smoothness term")
+    _check_args(poses, seq_3d_kps, iters, prior_weight, None, lam0)
+    F = np.asarray(poses).shape[0]
+    _check_prior_poses(prior_poses, F)
+    w_np, kps_np = _frame_weights(joint_weight, seq_3d_kps, F)
+    from .smplx_fk import lm_chain_starts, lm_chain_workspace_floats, lm_solve_chain
+    starts = lm_chain_starts(F, seq_starts)
+    from .inference import MAX_WINDOWS_PER_CALL
+    dev = smplx_model.device
+    iters, pw = int(iters), float(prior_weight)
+    S = starts.shape[0] - 1
+    lengths = np.diff(starts).astype(np.int64)
+    longest = int(lengths.max())
+    pad = starts[:-1, None].astype(np.int64) + np.arange(longest)[None]          # (S, longest) frame of each slot
+    live = np.arange(longest)[None] < lengths[:, None]
+    last = np.zeros(F, bool)
+    last[starts[1:] - 1] = True
+
+    th = torch.as_tensor(np.ascontiguousarray(np.asarray(poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
+    th0 = th if prior_poses is None else torch.as_tensor(
+        np.ascontiguousarray(np.asarray(prior_poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
+    target = _rel(torch.as_tensor(kps_np, device=dev))
+    wj = None if w_np is None else torch.as_tensor(w_np, device=dev)
+    row_w = None if wj is None else wj.repeat_interleave(3, dim=1).contiguous()
+    starts_d = torch.as_tensor(starts, device=dev)
+    seg = torch.as_tensor(np.repeat(np.arange(S), lengths), device=dev)
+    pad_d = torch.as_tensor(np.where(live, pad, 0), device=dev)
+    live_d = torch.as_tensor(live, device=dev)
+    tie = torch.as_tensor((~last[:-1]).astype(np.float32), device=dev)            # frame f has f + 1 in its sequence
+    b_all = None
+    if betas is not None:
+        b_all = torch.as_tensor(np.asarray(betas, np.float32)[:smplx_model.num_betas][None], device=dev)
+        b_all = b_all.expand(F, -1).contiguous()
+    chunks = [(s, min(MAX_WINDOWS_PER_CALL, F - s)) for s in range(0, F, MAX_WINDOWS_PER_CALL)]
+
+    def full_pose(t, s, n):
+        full = torch.zeros((n, 55, 3), device=dev)
+        full[:, :22] = t[s:s + n].reshape(n, 22, 3)
+        return full
+
+    def residual(t):
+        out = torch.empty((F, 17, 3), device=dev)
+        for s, n in chunks:
+            out[s:s + n] = _rel(smplx_model.joints(full_pose(t, s, n), None if b_all is None else b_all[s:s + n],
+                                                   None, None, select="coco"))
+        return (out - target).reshape(F, 51)
+
+    def cost_of(r, t):
+        sq = r.reshape(F, 17, 3).square().sum(2)
+        per = 0.5 * (sq if wj is None else sq * wj).sum(1) + 0.5 * pw * (t - th0).square().sum(1)
+        if F > 1:
+            per[:-1] += 0.5 * sw * tie * (t[1:] - t[:-1]).square().sum(1)
+        return torch.where(live_d, per[pad_d], torch.zeros((), device=dev)).sum(1)
+
+    with torch.no_grad():
+        th = th.clone()
+        lam = torch.full((S,), float(lam0), device=dev)
+        jr = torch.empty((F, 51, NUM_DOF), device=dev)
+        r = torch.empty((F, 51), device=dev)
+        work = torch.empty((lm_chain_workspace_floats(F, NUM_DOF),), device=dev)
+        hist = torch.empty((iters + 1, S), device=dev)
+        cost = cost_of(residual(th), th)
+        hist[0] = cost
+        for it in range(iters):
+            for s, n in chunks:
+                jac, joints = smplx_model.joints_jacobian(full_pose(th, s, n), None if b_all is None else b_all[s:s + n],
+                                                          None, None, select="coco")
+                r[s:s + n] = (_rel(joints) - target[s:s + n]).reshape(n, 51)
+                jr[s:s + n] = _rel(jac.reshape(n, 17, 3, NUM_DOF)).reshape(n, 51, NUM_DOF)
+            delta = lm_solve_chain(jr, r, lam, th, sw, mu=pw, prior=(th - th0).contiguous(), row_weight=row_w,
+                                   seq_starts=starts_d, workspace=work)
+            cand = th + delta
+            cc = cost_of(residual(cand), cand)
+            ok = cc < cost   # False for a NaN step
+            th = torch.where(ok[seg][:, None], cand, th)
+            cost = torch.where(ok, cc, cost)
+            lam = torch.where(ok, lam / 3.0, lam * 3.0)
+            hist[it + 1] = cost
+    return {"poses": th.cpu().numpy(), "cost": hist.cpu().numpy()}
+
+
 def _sequence_tensors(poses, seq_3d_kps, joint_weight, dev):
     th = torch.as_tensor(np.ascontiguousarray(np.asarray(poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
     F = th.shape[0]
@@ -222,7 +372,8 @@ def fit_shape(poses, seq_3d_kps, smplx_model, betas=None, shape_weight: float = 
 
 
 def refine_sequence(poses, seq_3d_kps, smplx_model, rounds: int = 3, iters: int = 5, prior_weight: float = 1e-2,
-                    shape_weight: float = 1e-3, joint_weight=None, lam0: float = 1e-2, betas=None) -> dict:
+                    shape_weight: float = 1e-3, joint_weight=None, lam0: float = 1e-2, betas=None,
+                    smooth_weight: float = 0.0) -> dict:
     """poses (F,66) solved by the IK, seq_3d_kps (F,17,3) COCO -> {"poses": (F,66)
     float32, "betas": (nb,) float32, "cost": (rounds+1,)}: `rounds` rounds of
     one shape step (fit_shape) followed by `iters` pose iterations
@@ -231,9 +382,14 @@ def refine_sequence(poses, seq_3d_kps, smplx_model, rounds: int = 3, iters: int 
     kept only where the total cost fell (a NaN step is rejected), and
     refine_poses never raises a frame's cost. The pose prior stays anchored at
     the input poses theta0 through all rounds. betas: the starting shape, None
-    = zero. rounds=0 returns the inputs."""
+    = zero. rounds=0 returns the inputs. smooth_weight > 0: the pose iterations
+    are refine_smooth's (the frames one sequence, 1/2 smooth_weight
+    sum_f |theta_{f+1} - theta_f|^2 part of the cost); 0 changes nothing."""
     _check_args(poses, seq_3d_kps, iters, prior_weight, joint_weight, lam0)
     _check_shape_args(smplx_model, betas, shape_weight)
+    smooth = float(smooth_weight)
+    if not smooth >= 0.0:
+        raise ValueError(f"smooth_weight must be >= 0, got {smooth_weight}")
     if int(rounds) < 0:
         raise ValueError(f"rounds must be >= 0, got {rounds}")
     rounds, sw, pw = int(rounds), float(shape_weight), float(prior_weight)
@@ -243,12 +399,15 @@ def refine_sequence(poses, seq_3d_kps, smplx_model, rounds: int = 3, iters: int 
     th = th0.copy()
 
     def frames(th_np, beta_np, n_it):
+        if smooth > 0.0:
+            return refine_smooth(th_np, seq_3d_kps, smplx_model, smooth, betas=beta_np, iters=n_it, prior_weight=pw,
+                                 joint_weight=joint_weight, lam0=lam0, prior_poses=th0)
         return refine_poses(th_np, seq_3d_kps, smplx_model, betas=beta_np, iters=n_it, prior_weight=pw,
                             joint_weight=joint_weight, lam0=lam0, prior_poses=th0)
 
     def total(per_frame, beta_np):
-        # per frame the data and prior terms as refine_poses itself computes them: its history never
-        # increases, so neither does this sum
+        # per frame (per sequence with smooth_weight) the terms as refine_poses (refine_smooth) itself
+        # computes them: its history never increases, so neither does this sum
         return float(per_frame.astype(np.float64).sum()) + 0.5 * sw * float(np.square(beta_np.astype(np.float64)).sum())
 
     cost = [total(frames(th, beta, 0)["cost"][0], beta)]

@@ -226,6 +226,105 @@ def lm_solve_sum(partial: torch.Tensor, mu: float = 0.0, lam: float = 0.0, prior
     return delta
 
 
+LM_CHAIN_MAX_N = 96              # include/tik.h, TIK_LM_CHAIN_MAX_N
+
+
+def lm_chain_starts(F: int, seq_starts=None) -> np.ndarray:
+    """The sequence boundaries lm_solve_chain takes: int32 (S+1,), sequence q the
+    frames seq_starts[q] .. seq_starts[q+1] - 1. None: one sequence, [0, F].
+    A pure host function. ValueError unless F >= 1 and the array is 1-D, of an
+    integer type, starts at 0, ascends strictly and ends at F."""
+    F = int(F)
+    if F < 1:
+        raise ValueError(f"F must be >= 1, got {F}")
+    if seq_starts is None:
+        return np.array([0, F], np.int32)
+    if isinstance(seq_starts, torch.Tensor):
+        seq_starts = seq_starts.detach().cpu().numpy()
+    s = np.asarray(seq_starts)
+    if s.ndim != 1 or s.shape[0] < 2:
+        raise ValueError(f"seq_starts must be a 1-D array of S + 1 >= 2 entries, got shape {s.shape}")
+    if not np.issubdtype(s.dtype, np.integer):
+        raise ValueError(f"seq_starts must hold integers, got {s.dtype}")
+    s = s.astype(np.int64)
+    if s[0] != 0 or s[-1] != F or not (np.diff(s) > 0).all():
+        raise ValueError(f"seq_starts must start at 0, ascend strictly and end at F = {F}, got {s.tolist()}")
+    return s.astype(np.int32)
+
+
+def lm_chain_workspace_floats(F: int, n: int) -> int:
+    """Floats of lm_solve_chain's workspace (tik_lm_chain_workspace_floats): F (n (n + 1) / 2 + n)."""
+    return int(F) * lm_partial_width(int(n))
+
+
+def lm_solve_chain(jac: torch.Tensor, r: torch.Tensor, lam: torch.Tensor, theta, smooth: float, mu: float = 0.0,
+                   prior=None, row_weight=None, seq_starts=None, workspace=None):
+    """One damped least-squares step per sequence with neighbouring frames tied
+    (tik_lm_solve_chain): the Gauss-Newton system of
+    sum_f [1/2 r_f^T W_f r_f + 1/2 mu |prior_f|^2] + 1/2 smooth sum_f |theta_{f+1} - theta_f|^2,
+    the sum over neighbours inside a sequence, with (mu + lam[q]) I on every
+    diagonal block of sequence q; block tridiagonal, solved by block Cholesky,
+    one workgroup per sequence. jac (F,m,n), r (F,m), lam (S), theta (F,n) (None
+    allowed only with smooth == 0), prior (F,n) or None (zero), row_weight (m) or
+    (F,m) non-negative or None (one); contiguous float32 on the device.
+    seq_starts: None (one sequence), a host array checked by lm_chain_starts, or
+    a device int32 tensor whose values lm_chain_starts has checked before (kept
+    resident across iterations; taken as it is, no copy back: a sequence with
+    bounds outside [0, F] does no work). workspace: None or
+    a contiguous float32 device tensor of at least lm_chain_workspace_floats(F, n)
+    elements; it holds the factors afterwards. n <= 96, m <= 768, mu >= 0,
+    smooth >= 0; mu + lam[q] > 0 is the caller's promise (a matrix that is not
+    positive gives NaN for the whole sequence, nothing else). -> delta (F,n)."""
+    if jac.dim() != 3:
+        raise ValueError(f"jac must be (F, m, n), got {tuple(jac.shape)}")
+    F, m, n = (int(s) for s in jac.shape)
+    if F < 1 or not 1 <= n <= LM_CHAIN_MAX_N or not 1 <= m <= LM_MAX_M:
+        raise ValueError(f"lm_solve_chain: need F >= 1, 1 <= m <= {LM_MAX_M}, 1 <= n <= {LM_CHAIN_MAX_N}; got {(F, m, n)}")
+    if tuple(r.shape) != (F, m):
+        raise ValueError(f"r must be {(F, m)}, got {tuple(r.shape)}")
+    if isinstance(seq_starts, torch.Tensor) and seq_starts.is_cuda:
+        starts = seq_starts
+        if starts.dtype != torch.int32 or starts.dim() != 1 or not 2 <= starts.shape[0] <= F + 1 or not starts.is_contiguous():
+            raise ValueError(f"a device seq_starts must be a contiguous int32 (S + 1,) tensor with 1 <= S <= {F}")
+    else:
+        starts = lm_chain_starts(F, seq_starts)
+    S = int(starts.shape[0]) - 1
+    if tuple(lam.shape) != (S,):
+        raise ValueError(f"lam must be {(S,)}, one value per sequence, got {tuple(lam.shape)}")
+    mu, smooth = float(mu), float(smooth)
+    if not mu >= 0.0:
+        raise ValueError(f"mu must be >= 0, got {mu}")
+    if not smooth >= 0.0:
+        raise ValueError(f"smooth must be >= 0, got {smooth}")
+    if theta is None and smooth != 0.0:
+        raise ValueError("theta may be None only with smooth == 0")
+    if theta is not None and tuple(theta.shape) != (F, n):
+        raise ValueError(f"theta must be {(F, n)}, got {tuple(theta.shape)}")
+    if prior is not None and tuple(prior.shape) != (F, n):
+        raise ValueError(f"prior must be {(F, n)}, got {tuple(prior.shape)}")
+    if row_weight is not None and tuple(row_weight.shape) not in ((m,), (F, m)):
+        raise ValueError(f"row_weight must be {(m,)} or {(F, m)}, got {tuple(row_weight.shape)}")
+    for name, t in (("jac", jac), ("r", r), ("lam", lam), ("theta", theta), ("prior", prior), ("row_weight", row_weight),
+                    ("workspace", workspace)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 tensor")
+    need = lm_chain_workspace_floats(F, n)
+    if workspace is not None and workspace.numel() < need:
+        raise ValueError(f"workspace must hold at least {need} floats, got {workspace.numel()}")
+    _lib.require_gpu(jac, r, lam, theta, prior, row_weight, workspace)
+    if not isinstance(starts, torch.Tensor):
+        starts = torch.from_numpy(starts).to(jac.device)
+    if workspace is None:
+        workspace = torch.empty((need,), device=jac.device, dtype=torch.float32)
+    delta = torch.empty((F, n), device=jac.device, dtype=torch.float32)
+    stride = m if row_weight is not None and row_weight.dim() == 2 else 0
+    _lib.check(_lib.load().tik_lm_solve_chain(jac.data_ptr(), r.data_ptr(), _lib.ptr(prior), _lib.ptr(theta),
+                                              _lib.ptr(row_weight), stride, lam.data_ptr(), starts.data_ptr(), mu, smooth,
+                                              F, S, m, n, workspace.data_ptr(), delta.data_ptr(), _lib.stream_of(jac)),
+               "lm_solve_chain")
+    return delta
+
+
 def split_pose156(P: torch.Tensor, apply_root_rot: bool = True) -> torch.Tensor:
     """AMASS pose rows (R,156) [root 3 | body 63 | lhand 45 | rhand 45] on the
     device -> full_pose (R,55,3) (jaw and eyes zero), smpl_util.py:58-66."""

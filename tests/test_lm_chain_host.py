@@ -1,0 +1,181 @@
+"""Host side of the temporally smooth refinement: smplx_fk.lm_chain_starts, the
+ValueError paths of lm_solve_chain, refine_smooth, refine_sequence and run_test
+(reached without loading the library), the --smooth argument, and the C ABI's
+two new entry points (declared, exported, refusing bad arguments before any
+device call). No GPU."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import REPO
+from temporal_inverse_kinematics_amd.smplx_fk import LM_CHAIN_MAX_N, lm_chain_starts, lm_solve_chain   # noqa: F401  (the feature)
+
+
+@pytest.fixture
+def no_library(monkeypatch):
+    from temporal_inverse_kinematics_amd import _lib
+
+    def refuse(*a, **k):
+        raise AssertionError("the validators must not touch the library")
+    monkeypatch.setattr(_lib, "load", refuse)
+
+
+def _bare_model():
+    """An SMPLX object without a handle: what the validators read, nothing else."""
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    m = object.__new__(SMPLX)
+    m.num_joints, m.num_static_joints, m.num_betas, m.device = 144, 127, 10, torch.device("cpu")
+    return m
+
+
+def test_lm_chain_starts_accepts():
+    F = 7
+    for given, want in ((None, [0, F]), ([0, F], [0, F]), ([0, 1, 3, F], [0, 1, 3, F]), (np.array([0, 4, F], np.int64), [0, 4, F]),
+                        (torch.tensor([0, 2, F]), [0, 2, F]), (list(range(F + 1)), list(range(F + 1)))):
+        got = lm_chain_starts(F, given)
+        assert isinstance(got, np.ndarray) and got.dtype == np.int32 and got.tolist() == want
+    assert lm_chain_starts(1).tolist() == [0, 1]
+
+
+@pytest.mark.parametrize("bad", [[1, 7], [0, 6], [0, 8], [0, 3, 3, 7], [0, 5, 2, 7], [], [0], np.array([0.0, 7.0]),
+                                 np.array([0.0, 3.5, 7.0]), [[0, 7]], [0, 7, 7], [-1, 0, 7]],
+                         ids=["not_from_0", "ends_early", "ends_late", "repeated", "descending", "empty", "one_entry", "float",
+                              "float_fraction", "two_d", "repeated_end", "negative"])
+def test_lm_chain_starts_refuses(bad):
+    with pytest.raises(ValueError):
+        lm_chain_starts(7, bad)
+
+
+def test_lm_chain_starts_refuses_no_frames():
+    for F in (0, -3):
+        with pytest.raises(ValueError):
+            lm_chain_starts(F)
+
+
+def test_lm_solve_chain_validates_before_the_library(no_library):
+    assert LM_CHAIN_MAX_N == 96
+    F, m, n = 4, 5, 3
+    J, r, lam, th = torch.zeros((F, m, n)), torch.zeros((F, m)), torch.ones(1), torch.zeros((F, n))
+    nan = float("nan")
+    bad = [dict(jac=J[0]), dict(r=r[:, :4]), dict(r=r[0]), dict(lam=torch.ones(2)), dict(lam=torch.ones(2), seq_starts=[0, F]),
+           dict(seq_starts=[0, 2, F]), dict(theta=None), dict(theta=th[:3]), dict(theta=th.double()), dict(smooth=-1.0),
+           dict(smooth=nan), dict(mu=-0.1), dict(mu=nan), dict(prior=th[:, :2]), dict(row_weight=torch.zeros(4)),
+           dict(row_weight=torch.zeros((3, m))), dict(row_weight=torch.zeros((F, m), dtype=torch.float64)),
+           dict(jac=torch.zeros((F, m, 97)), theta=torch.zeros((F, 97))), dict(jac=torch.zeros((F, 769, n)), r=torch.zeros((F, 769))),
+           dict(jac=torch.zeros((0, m, n))), dict(jac=J.double()), dict(jac=torch.zeros((F, m, 6))[:, :, ::2]),
+           dict(seq_starts=[1, F]), dict(seq_starts=[0, F - 1]), dict(seq_starts=[0, 2, 2, F]), dict(seq_starts=[0, 3, 2, F]),
+           dict(seq_starts=[]), dict(seq_starts=np.array([0.0, F])), dict(workspace=torch.zeros(F * (6 + 3) - 1)),
+           dict(workspace=torch.zeros(F * 9, dtype=torch.float64))]
+    for kw in bad:
+        a = dict(jac=J, r=r, lam=lam, theta=th, smooth=0.5)
+        a.update(kw)
+        with pytest.raises(ValueError):
+            lm_solve_chain(**a)
+    with pytest.raises(RuntimeError, match="GPU"):   # valid arguments on the CPU: refused, no fallback
+        lm_solve_chain(J, r, lam, th, 0.5)
+    with pytest.raises(RuntimeError, match="GPU"):
+        lm_solve_chain(J, r, torch.ones(2), None, 0.0, row_weight=torch.ones((F, m)), seq_starts=[0, 1, F])
+
+
+def test_refine_smooth_validates_before_the_library(no_library):
+    from temporal_inverse_kinematics_amd.refine import refine_sequence, refine_smooth
+    m = _bare_model()
+    F = 3
+    poses, kps = np.zeros((F, 66), np.float32), np.zeros((F, 17, 3), np.float32)
+    for sw in (0, 0.0, -1e-3, float("nan")):
+        with pytest.raises(ValueError, match="refine_poses"):
+            refine_smooth(poses, kps, m, sw)
+    for kw in (dict(joint_weight=np.ones(16)), dict(joint_weight=np.ones((F + 1, 17))), dict(joint_weight=np.ones((F, 16))),
+               dict(joint_weight=np.ones((17, F))), dict(joint_weight=-np.ones(17)), dict(joint_weight=-np.ones((F, 17))),
+               dict(iters=-1), dict(prior_weight=0), dict(prior_weight=float("nan")), dict(lam0=0.0),
+               dict(prior_poses=poses[:2]), dict(seq_starts=[0, 2]), dict(seq_starts=[1, F]), dict(seq_starts=[0, 2, 2, F]),
+               dict(seq_starts=[0.0, 3.0])):
+        with pytest.raises(ValueError):
+            refine_smooth(poses, kps, m, 0.1, **kw)
+    with pytest.raises(ValueError):
+        refine_smooth(poses[:, :60], kps, m, 0.1)
+    with pytest.raises(ValueError):
+        refine_smooth(poses, kps[:2], m, 0.1)
+    with pytest.raises(TypeError):
+        refine_smooth(poses, kps, m)            # smooth_weight has no default
+    for sw in (-0.1, float("nan")):
+        with pytest.raises(ValueError, match="smooth_weight"):
+            refine_sequence(poses, kps, m, smooth_weight=sw)
+
+
+def test_missing_keypoints_become_zero_weights():
+    from temporal_inverse_kinematics_amd.refine import _frame_weights
+    F = 4
+    kps = np.random.default_rng(0).normal(0, 1, (F, 17, 3)).astype(np.float32)
+    w, k = _frame_weights(None, kps, F)
+    assert w is None and np.array_equal(k, kps)
+    w, k = _frame_weights(np.arange(17), kps, F)
+    assert w.shape == (F, 17) and w.dtype == np.float32 and np.array_equal(w[2], np.arange(17))
+    holes = kps.copy()
+    holes[1, 9, 2] = np.nan          # one coordinate of a wrist
+    holes[2, 11] = np.inf            # a hip: the whole frame
+    holes[3] = np.nan
+    given = np.full((F, 17), 2.0, np.float32)
+    w, k = _frame_weights(given, holes, F)
+    assert np.isfinite(k).all() and np.array_equal(k[0], kps[0])
+    assert np.array_equal(k[1, 9], np.zeros(3)) and np.array_equal(k[1, :9], kps[1, :9])
+    assert (w[0] == 2).all() and w[1, 9] == 0 and (np.delete(w[1], 9) == 2).all()
+    assert (w[2] == 0).all() and (w[3] == 0).all()
+    assert (given == 2).all() and np.isnan(holes[1, 9, 2])          # the caller's arrays are left alone
+    w, _ = _frame_weights(None, holes, F)
+    assert (w[0] == 1).all() and w[1, 9] == 0 and (w[2:] == 0).all()
+
+
+def test_smooth_argument_parses(no_library):
+    from temporal_inverse_kinematics_amd import inference
+    p = inference.build_parser()
+    a = p.parse_args(["seq.npz", "synthetic", "--refine", "5", "--smooth", "0.1", "--check"])
+    assert a.smooth == 0.1 and a.refine == 5 and a.check and a.fit_shape == 0
+    assert p.parse_args(["seq.npz"]).smooth == 0.0
+    assert p.parse_args(["seq.npz", "synthetic", "--refine", "5", "--fit-shape", "2", "--smooth", "1"]).smooth == 1.0
+    with pytest.raises(SystemExit):
+        p.parse_args(["seq.npz", "--smooth", "much"])
+    for argv in (["seq.npz", "--refine", "2", "--smooth", "0.1"],                # no SMPL-X dir
+                 ["seq.npz", "synthetic", "--smooth", "0.1"],                    # no pose iterations
+                 ["seq.npz", "synthetic", "--refine", "0", "--smooth", "0.1"],
+                 ["seq.npz", "synthetic", "--refine", "2", "--smooth", "-1"],
+                 ["seq.npz", "synthetic", "--refine", "2", "--smooth", "nan"]):
+        with pytest.raises(SystemExit):
+            inference.main(argv)
+    with pytest.raises(ValueError, match="smooth"):
+        inference.run_test("seq.npz", None, refine=2, smooth=0.1)
+    with pytest.raises(ValueError, match="smooth"):
+        inference.run_test("seq.npz", "synthetic", refine=0, smooth=0.1)
+    with pytest.raises(ValueError, match="smooth"):
+        inference.run_test("seq.npz", "synthetic", refine=2, smooth=-0.1)
+    with pytest.raises(ValueError, match="smooth"):
+        inference.run_test("seq.npz", "synthetic", refine=2, smooth=float("nan"))
+
+
+def test_header_declares_and_library_exports_the_entry_points():
+    from temporal_inverse_kinematics_amd import _build, _lib
+    txt = open(os.path.join(REPO, "include", "tik.h")).read()
+    assert re.search(r"^int tik_lm_solve_chain\(", txt, re.M) and re.search(r"^size_t tik_lm_chain_workspace_floats\(", txt, re.M)
+    assert re.search(r"^#define TIK_LM_CHAIN_MAX_N 96\b", txt, re.M)
+    for name in ("tik_lm_solve_chain", "tik_lm_chain_workspace_floats"):
+        assert name in _lib.SIGNATURES
+    _build.build()
+    lib = _lib.load()
+    assert lib.tik_lm_chain_workspace_floats(8, 66) == 8 * (66 * 67 // 2 + 66)
+    assert lib.tik_lm_chain_workspace_floats(0, 66) == 0 and lib.tik_lm_chain_workspace_floats(8, 0) == 0
+    one = (_lib.ctypes.c_float * 4)()
+    p = _lib.ctypes.addressof(one)
+    nan = float("nan")
+
+    def call(jac=p, r=p, prior=None, theta=p, row_w=None, stride=0, lam=p, starts=p, mu=0.1, smooth=0.1, F=1, S=1, m=1, n=1,
+             ws=p, delta=p):
+        return lib.tik_lm_solve_chain(jac, r, prior, theta, row_w, stride, lam, starts, mu, smooth, F, S, m, n, ws, delta, None)
+    # refused on the host, before any device call
+    for kw in (dict(jac=None), dict(r=None), dict(lam=None), dict(starts=None), dict(ws=None), dict(delta=None), dict(theta=None),
+               dict(F=0), dict(F=-2), dict(S=0), dict(S=2), dict(n=0), dict(n=97), dict(m=0), dict(m=769), dict(mu=-1.0),
+               dict(mu=nan), dict(smooth=-1.0), dict(smooth=nan), dict(stride=2), dict(row_w=p, stride=-1)):
+        assert call(**kw) == _lib.TIK_E_INVALID, kw
+        assert "tik_lm_solve_chain" in _lib.last_error()
