@@ -149,11 +149,14 @@ def test_fk_sparse_skinning(consts, monkeypatch, nzmax):
 
 @pytest.mark.parametrize("B", [1, 1025, 2500, 4096])
 def test_fk_chunk_pipeline_batch_invariant(consts, B):
-    """Batches of more than one 1024-body chunk run blend + skinning per chunk,
-    the chunks alternating between two HIP streams (fk_forward.cpp): every body's
-    vertices and joints are bit-identical to the same body solved alone (the
-    chunking only partitions rows), at one body, a chunk plus one, a ragged
-    last chunk and config #4's batch; sampled bodies against the oracle."""
+    """Batches of more than one 2048-body chunk (fk_model.h) run blend + skinning
+    per chunk, the chunks alternating between two HIP streams (fk_forward.cpp):
+    every body's vertices and joints are bit-identical to the same body solved
+    alone (the chunking only partitions rows), at one body, half a chunk plus
+    one (one chunk), a ragged second chunk and config #4's two full chunks; the
+    sampled bodies include both sides of the chunk boundary (2047, 2048); the
+    last body against the oracle. Three chunks, the third on the first chunk's
+    buffer: tests/test_gpu_fk_oracle.py with TIK_FK_CHUNK=4."""
     from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
     pose, betas, expr, transl = _inputs(B, 900 + B)
     cu = lambda a: torch.from_numpy(a).cuda()
@@ -161,7 +164,7 @@ def test_fk_chunk_pipeline_batch_invariant(consts, B):
     j, v = m.full_forward(cu(pose), cu(betas), cu(expr), cu(transl))
     torch.cuda.synchronize()
     assert torch.isfinite(v).all()
-    for i in sorted({0, min(1023, B - 1), min(1024, B - 1), B - 1}):
+    for i in sorted({0, min(1023, B - 1), min(1024, B - 1), min(2047, B - 1), min(2048, B - 1), B - 1}):
         j1, v1 = m.full_forward(cu(pose[i:i + 1]), cu(betas[i:i + 1]), cu(expr[i:i + 1]), cu(transl[i:i + 1]))
         assert torch.equal(v[i:i + 1], v1) and torch.equal(j[i:i + 1], j1), i
     _, vr = sl.smplx_forward(consts, pose[-1:], betas[-1:], expr[-1:], transl[-1:])

@@ -35,14 +35,8 @@ def cu(a):
 
 
 def oracle_bins(c, pose):
-    """The contour bin of each body, from the oracle's own functions (smplx_forward keeps it to itself)."""
-    p = np.asarray(pose, np.float64).reshape(-1, 55, 3) + c["pose_mean"].astype(np.float64).reshape(1, 55, 3)
-    R = sl.batch_rodrigues(p.reshape(-1, 3)).reshape(-1, 55, 3, 3)
-    rel = np.broadcast_to(np.eye(3), (R.shape[0], 3, 3)).copy()
-    for j in sl.neck_kin_chain(c["parents"].astype(np.int64)):
-        rel = R[:, j] @ rel
-    y = np.round(np.minimum(-sl.rot_mat_to_euler(rel) * 180.0 / np.pi, 39)).astype(np.int64)
-    return np.where(y < 0, np.where(y < -39, 78, 39 - y), y)
+    """The contour bin of each body: the oracle's own bin logic (smplx_lbs.contour_bins)."""
+    return sl.contour_bins(c, pose)
 
 
 def oracle_joints(B, bare=False):
