@@ -62,20 +62,10 @@ def fk_check(poses, seq_3d_kps, smplx_model, betas=None) -> dict:
     mesh) and the keypoints are both made root-relative (mean of COCO 11/12,
     the hips). -> {"per_joint": (F,17) distances on the host, "mpjpe": (F,),
     "mean": float}."""
-    from .smplx_fk import split_pose156
-    dev = smplx_model.device
-    p = torch.as_tensor(np.ascontiguousarray(poses, dtype=np.float32), device=dev)
-    F = p.shape[0]
-    P = torch.zeros((F, 156), device=dev)
-    P[:, :66] = p[:, :66]
-    b = None
-    if betas is not None:
-        b = torch.as_tensor(np.asarray(betas, np.float32)[:smplx_model.num_betas][None], device=dev).expand(F, -1).contiguous()
+    from .refine import _FKView, _upload
+    th, _, kps, beta = _upload(smplx_model, poses, seq_3d_kps, betas=betas)
     with torch.no_grad():
-        fk = smplx_model.joints(split_pose156(P), b, None, None, select="coco")
-    kps = torch.as_tensor(np.ascontiguousarray(seq_3d_kps, dtype=np.float32), device=dev).reshape(F, 17, 3)
-    rel = lambda x: x - 0.5 * (x[:, 11:12] + x[:, 12:13])
-    per_joint = (rel(fk) - rel(kps)).norm(dim=2).cpu().numpy()
+        per_joint = _FKView(smplx_model, kps, beta).residual(th).norm(dim=2).cpu().numpy()
     mpjpe = per_joint.mean(axis=1)
     return {"per_joint": per_joint, "mpjpe": mpjpe, "mean": float(mpjpe.mean())}
 

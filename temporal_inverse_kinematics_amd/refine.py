@@ -40,24 +40,31 @@ refine_poses plus smooth_weight c_f I (c_f neighbours), every off-diagonal
 block -smooth_weight I; smplx_fk.lm_solve_chain (tik_lm_solve_chain) solves a
 whole sequence in one workgroup. Weights per frame and keypoint let a keypoint,
 or a whole frame, that was not detected be filled from the neighbours.
+
+The drivers share their pieces: _upload (host to device, once per call),
+_chunks (the one reader of inference.MAX_WINDOWS_PER_CALL), _FKView (r, J and
+Jb of a run of frames), _data_term and _lm_loop (the accept rule).
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from .smplx_fk import LM_RUN, lm_accumulate, lm_partial_width, lm_solve, lm_solve_sum
+from . import inference
+from .smplx_fk import (LM_RUN, lm_accumulate, lm_chain_starts, lm_chain_workspace_floats, lm_partial_width, lm_solve,
+                       lm_solve_chain, lm_solve_sum)
 
 NUM_DOF = 66
 
 
 def _rel(x: torch.Tensor) -> torch.Tensor:
-    """Root-relative as inference.fk_check: minus the mean of COCO 11 and 12, along dim 1."""
+    """Root-relative: minus the mean of COCO 11 and 12 (the hips), along dim 1."""
     return x - 0.5 * (x[:, 11:12] + x[:, 12:13])
 
 
-def _check_args(poses, seq_3d_kps, iters, prior_weight, joint_weight, lam0):
-    """The ValueErrors of refine_poses, before any device work."""
+# ---------------------------------------------------------------- argument checks, before any device work
+def _check_frames(poses, seq_3d_kps) -> int:
+    """poses (F, >= 66) and as many keypoints (F,17,3) -> F."""
     p = np.asarray(poses)
     if p.ndim != 2 or p.shape[1] < NUM_DOF:
         raise ValueError(f"poses must be (F, >= {NUM_DOF}), got {p.shape}")
@@ -65,6 +72,10 @@ def _check_args(poses, seq_3d_kps, iters, prior_weight, joint_weight, lam0):
     F = p.shape[0]
     if int(np.prod(k)) != F * 51:
         raise ValueError(f"seq_3d_kps must be ({F}, 17, 3), got {tuple(k)}")
+    return F
+
+
+def _check_lm_scalars(iters, prior_weight, lam0):
     if int(iters) < 0:
         raise ValueError(f"iters must be >= 0, got {iters}")
     if not float(prior_weight) > 0.0:
@@ -72,10 +83,18 @@ def _check_args(poses, seq_3d_kps, iters, prior_weight, joint_weight, lam0):
                          "the prior toward the solved pose is what makes the problem well-posed")
     if not float(lam0) > 0.0:
         raise ValueError(f"lam0 must be > 0, got {lam0}")
-    if joint_weight is not None:
-        w = np.asarray(joint_weight, np.float32)
-        if w.shape != (17,) or not (w >= 0).all():
-            raise ValueError("joint_weight must be 17 non-negative values (COCO order)")
+
+
+def _check_joint_weight(joint_weight, F=None):
+    """None, or non-negative weights (17,), with a frame count F also (F,17) -> None or the float32 array."""
+    if joint_weight is None:
+        return None
+    w = np.asarray(joint_weight, np.float32)
+    shapes = ((17,),) if F is None else ((17,), (F, 17))
+    if w.shape not in shapes or not (w >= 0).all():
+        raise ValueError(f"joint_weight must be {' or '.join(map(str, shapes))} non-negative values (COCO order), "
+                         f"got shape {w.shape}")
+    return w
 
 
 def _check_prior_poses(prior_poses, F):
@@ -86,7 +105,7 @@ def _check_prior_poses(prior_poses, F):
 
 
 def _check_shape_args(smplx_model, betas, shape_weight):
-    """The ValueErrors of the shape step, before any device work. -> the number of betas."""
+    """The ValueErrors of the shape step."""
     if not float(shape_weight) > 0.0:
         raise ValueError("shape_weight must be > 0: a short or static sequence does not determine 10 shape values, "
                          "the prior toward the mean shape is what keeps the summed system positive definite")
@@ -97,6 +116,128 @@ def _check_shape_args(smplx_model, betas, shape_weight):
             raise ValueError(f"betas must be ({'nb' if nb is None else nb},) finite values, got shape {b.shape}")
 
 
+# ---------------------------------------------------------------- the shared pieces
+def _upload(smplx_model, poses, seq_3d_kps, prior_poses=None, betas=None):
+    """Host arrays -> float32 tensors on the model's device: (theta (F,66), theta0 (F,66): theta itself
+    without prior_poses, keypoints (F,17,3), beta (nb,) or None)."""
+    dev = smplx_model.device
+
+    def pose(p):
+        return torch.as_tensor(np.ascontiguousarray(np.asarray(p, dtype=np.float32)[:, :NUM_DOF]), device=dev)
+
+    th = pose(poses)
+    th0 = th if prior_poses is None else pose(prior_poses)
+    kps = torch.as_tensor(np.ascontiguousarray(seq_3d_kps, dtype=np.float32), device=dev).reshape(th.shape[0], 17, 3)
+    beta = None if betas is None else torch.as_tensor(np.asarray(betas, np.float32)[:smplx_model.num_betas], device=dev)
+    return th, th0, kps, beta
+
+
+def _chunks(F: int):
+    """[(first frame, frames)] of the runs of at most inference.MAX_WINDOWS_PER_CALL frames that one
+    library call takes; the length is read now, not at import."""
+    c = inference.MAX_WINDOWS_PER_CALL
+    return [(s, min(c, F - s)) for s in range(0, F, c)]
+
+
+def _rows(t, s: int, n: int):
+    """t[s:s + n]; t itself where that is all of it or t is None (one chunk is the usual case, and
+    every slice is a few microseconds of host time in calls that take a few hundred)."""
+    return t if t is None or (s == 0 and n == t.shape[0]) else t[s:s + n]
+
+
+def _joined(parts, dim: int):
+    """torch.cat(parts, dim), without the copy where there is one part."""
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim)
+
+
+class _FKView:
+    """The FK of a run of n frames against their keypoints (n,17,3), all with the body shape beta
+    ((nb,) device tensor, None: the mean shape): the residual r of the module docstring and its
+    Jacobians, rows made root-relative. th is always (n,66) on the device; the library sees the
+    frames in _chunks."""
+
+    def __init__(self, smplx_model, kps, beta=None):
+        self.model, self.n = smplx_model, kps.shape[0]
+        self.target = _rel(kps)
+        self.chunks = _chunks(self.n)
+        self.full = torch.zeros((self.n, 55, 3), device=kps.device)   # the hands, jaw and eyes stay zero
+        self.set_beta(beta)
+
+    def set_beta(self, beta):
+        """Another body shape for the same frames and keypoints."""
+        self.betas = None if beta is None else beta[None].expand(self.n, -1).contiguous()
+
+    def _inputs(self, th):
+        """-> per chunk (first frame, frames, full_pose rows, betas rows)."""
+        self.full[:, :22] = th.reshape(self.n, 22, 3)
+        return [(s, n, _rows(self.full, s, n), _rows(self.betas, s, n)) for s, n in self.chunks]
+
+    def coco(self, th):
+        """-> FK COCO-17 joints (n,17,3)."""
+        out = torch.empty((self.n, 17, 3), device=th.device)
+        for s, n, full, b in self._inputs(th):
+            self.model.joints(full, b, None, None, select="coco", out=_rows(out, s, n))
+        return out
+
+    def _residual_of(self, joints, s=0):
+        return _rel(joints) - _rows(self.target, s, joints.shape[0])
+
+    def residual(self, th):
+        """-> r (n,17,3)."""
+        return self._residual_of(self.coco(th))
+
+    def _linearize(self, jacobian, th, k):
+        def one(s, n, full, b):
+            jac, joints = jacobian(full, b, None, None, select="coco")
+            return (_rel(jac.reshape(n, 17, 3, k)).reshape(n, 51, k).contiguous(),
+                    self._residual_of(joints, s).reshape(n, 51).contiguous())
+        parts = self._inputs(th)
+        if len(parts) == 1:                  # nothing to put together: no copy
+            return one(*parts[0])
+        jr, r = torch.empty((self.n, 51, k), device=th.device), torch.empty((self.n, 51), device=th.device)
+        for s, n, full, b in parts:
+            jr[s:s + n], r[s:s + n] = one(s, n, full, b)
+        return jr, r
+
+    def linearize(self, th):
+        """-> (J (n,51,66) with respect to th, r (n,51))."""
+        return self._linearize(self.model.joints_jacobian, th, NUM_DOF)
+
+    def linearize_shape(self, th):
+        """-> (Jb (n,51,nb) with respect to the betas, r (n,51))."""
+        return self._linearize(self.model.joints_shape_jacobian, th, self.model.num_betas)
+
+
+def _data_term(r, w=None, per_frame: bool = True):
+    """1/2 sum_k w_k |r_k|^2: r (n,17,3) or (n,51), w None (one), (17,) or (n,17) -> (n,) per frame,
+    or the 0-d sum over all n frames."""
+    sq = r.reshape(-1, 17, 3).square().sum(2)
+    sq = sq if w is None else sq * w
+    return 0.5 * (sq.sum(1) if per_frame else sq.sum())
+
+
+def _lm_loop(th, cost, lam, iters, step, cost_of, frames_of):
+    """The Levenberg-Marquardt policy. A unit is what is accepted or rejected as a whole and has
+    one lambda: a frame, or a sequence of frames. th (n,k) the starting poses, cost (units,)
+    their cost, lam (units,); step(th, lam) -> delta (n,k); cost_of(th) -> (units,);
+    frames_of(ok (units,) bool) -> (n,) bool, each frame's verdict. Per iteration: the candidate
+    th + delta is kept for the units whose cost fell (lambda <- lambda / 3), the old poses for the
+    others (lambda <- 3 lambda); a NaN cost is no fall. -> (poses (n,k), history (iters+1, units):
+    row 0 `cost`, row it + 1 the cost after iteration it; it never increases). Pure torch."""
+    hist = cost.new_empty((iters + 1,) + tuple(cost.shape))
+    hist[0] = cost
+    for it in range(iters):
+        cand = th + step(th, lam)
+        cc = cost_of(cand)
+        ok = cc < cost   # False for a NaN step
+        th = torch.where(frames_of(ok)[:, None], cand, th)
+        cost = torch.where(ok, cc, cost)
+        lam = torch.where(ok, lam / 3.0, lam * 3.0)
+        hist[it + 1] = cost
+    return th, hist
+
+
+# ---------------------------------------------------------------- the drivers
 def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, prior_weight: float = 1e-2,
                  joint_weight=None, lam0: float = 1e-2, prior_poses=None) -> dict:
     """poses (F,66) solved by the IK, seq_3d_kps (F,17,3) COCO -> {"poses": (F,66)
@@ -105,66 +246,43 @@ def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, pr
     iteration; it never increases). prior_poses: None (the prior pulls toward
     `poses`) or (F,66), the theta0 of the cost when `poses` is a later iterate.
 
-    Per frame and iteration: the LM step from the current pose, the candidate's
-    cost with SMPLX.joints, accepted where the cost fell (lambda <- lambda / 3),
-    the old pose kept elsewhere (lambda <- 3 lambda); a NaN step counts as
-    rejected. All on the device with torch.where, no host round trip inside an
-    iteration; the cost history is copied once at the end. Frames go through in
-    chunks of at most inference.MAX_WINDOWS_PER_CALL."""
-    _check_args(poses, seq_3d_kps, iters, prior_weight, joint_weight, lam0)
-    _check_prior_poses(prior_poses, np.asarray(poses).shape[0])
-    from .inference import MAX_WINDOWS_PER_CALL
-    dev = smplx_model.device
+    Per frame and iteration (_lm_loop, a frame the unit): the LM step from the
+    current pose, the candidate's cost with SMPLX.joints, accepted where the
+    cost fell (lambda <- lambda / 3), the old pose kept elsewhere (lambda <- 3
+    lambda); a NaN step counts as rejected. All on the device with torch.where,
+    no host round trip inside an iteration; the cost history is copied once at
+    the end. Frames go through in chunks of at most
+    inference.MAX_WINDOWS_PER_CALL, all iterations of one chunk before the
+    next, so the Jacobians of one chunk are all that is resident."""
+    F = _check_frames(poses, seq_3d_kps)
+    _check_lm_scalars(iters, prior_weight, lam0)
+    w = _check_joint_weight(joint_weight)
+    _check_prior_poses(prior_poses, F)
     iters, pw = int(iters), float(prior_weight)
-    th_all = torch.as_tensor(np.ascontiguousarray(np.asarray(poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
-    F = th_all.shape[0]
-    pr_all = th_all if prior_poses is None else torch.as_tensor(
-        np.ascontiguousarray(np.asarray(prior_poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
-    kps_all = torch.as_tensor(np.ascontiguousarray(seq_3d_kps, dtype=np.float32), device=dev).reshape(F, 17, 3)
-    wj = None if joint_weight is None else torch.as_tensor(np.asarray(joint_weight, np.float32), device=dev)
+    th_all, pr_all, kps, beta = _upload(smplx_model, poses, seq_3d_kps, prior_poses, betas)
+    dev = th_all.device
+    wj = None if w is None else torch.as_tensor(w, device=dev)
     row_w = None if wj is None else wj.repeat_interleave(3).contiguous()
-    out = torch.empty((F, NUM_DOF), device=dev)
-    hist = torch.empty((iters + 1, F), device=dev)
+    out, hist = [], []
 
     with torch.no_grad():
-        for s in range(0, F, MAX_WINDOWS_PER_CALL):
-            n = min(MAX_WINDOWS_PER_CALL, F - s)
-            th0 = pr_all[s:s + n]
-            target = _rel(kps_all[s:s + n])
-            b = None
-            if betas is not None:
-                b = torch.as_tensor(np.asarray(betas, np.float32)[:smplx_model.num_betas][None], device=dev)
-                b = b.expand(n, -1).contiguous()
-            full = torch.zeros((n, 55, 3), device=dev)
+        for s, n in _chunks(F):
+            fk = _FKView(smplx_model, _rows(kps, s, n), beta)
+            th0 = _rows(pr_all, s, n)
 
-            def full_pose(th):
-                full[:, :22] = th.reshape(n, 22, 3)
-                return full
+            def cost_of(th):
+                return _data_term(fk.residual(th), wj) + 0.5 * pw * (th - th0).square().sum(1)
 
-            def cost_of(r, th):
-                sq = r.reshape(n, 17, 3).square().sum(2)
-                data = (sq if wj is None else sq * wj).sum(1)
-                return 0.5 * data + 0.5 * pw * (th - th0).square().sum(1)
+            def step(th, lam):
+                jr, r = fk.linearize(th)
+                return lm_solve(jr, r, lam, mu=pw, prior=(th - th0).contiguous(), row_weight=row_w)
 
-            th = th_all[s:s + n].clone()
+            th = _rows(th_all, s, n)
             lam = torch.full((n,), float(lam0), device=dev)
-            cost = cost_of((_rel(smplx_model.joints(full_pose(th), b, None, None, select="coco")) - target).reshape(n, 51), th)
-            hist[0, s:s + n] = cost
-            for it in range(iters):
-                jac, joints = smplx_model.joints_jacobian(full_pose(th), b, None, None, select="coco")
-                r = (_rel(joints) - target).reshape(n, 51).contiguous()
-                jr = _rel(jac.reshape(n, 17, 3, NUM_DOF)).reshape(n, 51, NUM_DOF).contiguous()
-                delta = lm_solve(jr, r, lam, mu=pw, prior=(th - th0).contiguous(), row_weight=row_w)
-                cand = th + delta
-                rc = (_rel(smplx_model.joints(full_pose(cand), b, None, None, select="coco")) - target).reshape(n, 51)
-                cc = cost_of(rc, cand)
-                ok = cc < cost   # False for a NaN step
-                th = torch.where(ok[:, None], cand, th)
-                cost = torch.where(ok, cc, cost)
-                lam = torch.where(ok, lam / 3.0, lam * 3.0)
-                hist[it + 1, s:s + n] = cost
-            out[s:s + n] = th
-    return {"poses": out.cpu().numpy(), "cost": hist.cpu().numpy()}
+            th, h = _lm_loop(th, cost_of(th), lam, iters, step, cost_of, lambda ok: ok)
+            out.append(th)
+            hist.append(h)
+    return {"poses": _joined(out, 0).cpu().numpy(), "cost": _joined(hist, 1).cpu().numpy()}
 
 
 def _frame_weights(joint_weight, seq_3d_kps, F):
@@ -172,12 +290,7 @@ def _frame_weights(joint_weight, seq_3d_kps, F):
     (weights (F,17) float32, or None where every weight is one; keypoints float32 with the missing ones
     zeroed). ValueError on a bad shape or a negative weight. Host only."""
     kps = np.array(seq_3d_kps, dtype=np.float32).reshape(F, 17, 3)
-    w = None
-    if joint_weight is not None:
-        w = np.asarray(joint_weight, np.float32)
-        if w.shape not in ((17,), (F, 17)) or not (w >= 0).all():
-            raise ValueError(f"joint_weight must be (17,) or ({F}, 17) non-negative values (COCO order), "
-                             f"got shape {w.shape}")
+    w = _check_joint_weight(joint_weight, F)
     seen = np.isfinite(kps).all(2)
     if not seen.all():
         w = np.ones((F, 17), np.float32) if w is None else np.broadcast_to(w, (F, 17)).copy()
@@ -213,8 +326,9 @@ def refine_smooth(poses, seq_3d_kps, smplx_model, smooth_weight, betas=None, ite
     hips): all its 17 weights become 0, its pose comes from the neighbours and
     the prior.
 
-    Per iteration: the FK Jacobians in chunks of inference.MAX_WINDOWS_PER_CALL
-    into one (F,51,66) buffer, one smplx_fk.lm_solve_chain call (block
+    Per iteration (_lm_loop, a sequence the unit): the FK Jacobians of all F
+    frames, (F,51,66), the library called in chunks of
+    inference.MAX_WINDOWS_PER_CALL, one smplx_fk.lm_solve_chain call (block
     tridiagonal, one workgroup per sequence), the candidate's cost with
     SMPLX.joints, accepted per sequence where its cost fell (lambda <- lambda /
     3), the old poses kept elsewhere (lambda <- 3 lambda); a NaN step counts as
@@ -226,14 +340,11 @@ def refine_smooth(poses, seq_3d_kps, smplx_model, smooth_weight, betas=None, ite
     if not sw > 0.0:
         raise ValueError(f"smooth_weight must be > 0, got {smooth_weight}: refine_poses is the refinement "
                          "without the smoothness term")
-    _check_args(poses, seq_3d_kps, iters, prior_weight, None, lam0)
-    F = np.asarray(poses).shape[0]
+    F = _check_frames(poses, seq_3d_kps)
+    _check_lm_scalars(iters, prior_weight, lam0)
     _check_prior_poses(prior_poses, F)
     w_np, kps_np = _frame_weights(joint_weight, seq_3d_kps, F)
-    from .smplx_fk import lm_chain_starts, lm_chain_workspace_floats, lm_solve_chain
     starts = lm_chain_starts(F, seq_starts)
-    from .inference import MAX_WINDOWS_PER_CALL
-    dev = smplx_model.device
     iters, pw = int(iters), float(prior_weight)
     S = starts.shape[0] - 1
     lengths = np.diff(starts).astype(np.int64)
@@ -243,10 +354,8 @@ def refine_smooth(poses, seq_3d_kps, smplx_model, smooth_weight, betas=None, ite
     last = np.zeros(F, bool)
     last[starts[1:] - 1] = True
 
-    th = torch.as_tensor(np.ascontiguousarray(np.asarray(poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
-    th0 = th if prior_poses is None else torch.as_tensor(
-        np.ascontiguousarray(np.asarray(prior_poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
-    target = _rel(torch.as_tensor(kps_np, device=dev))
+    th, th0, kps, beta = _upload(smplx_model, poses, kps_np, prior_poses, betas)
+    dev = th.device
     wj = None if w_np is None else torch.as_tensor(w_np, device=dev)
     row_w = None if wj is None else wj.repeat_interleave(3, dim=1).contiguous()
     starts_d = torch.as_tensor(starts, device=dev)
@@ -254,79 +363,25 @@ def refine_smooth(poses, seq_3d_kps, smplx_model, smooth_weight, betas=None, ite
     pad_d = torch.as_tensor(np.where(live, pad, 0), device=dev)
     live_d = torch.as_tensor(live, device=dev)
     tie = torch.as_tensor((~last[:-1]).astype(np.float32), device=dev)            # frame f has f + 1 in its sequence
-    b_all = None
-    if betas is not None:
-        b_all = torch.as_tensor(np.asarray(betas, np.float32)[:smplx_model.num_betas][None], device=dev)
-        b_all = b_all.expand(F, -1).contiguous()
-    chunks = [(s, min(MAX_WINDOWS_PER_CALL, F - s)) for s in range(0, F, MAX_WINDOWS_PER_CALL)]
-
-    def full_pose(t, s, n):
-        full = torch.zeros((n, 55, 3), device=dev)
-        full[:, :22] = t[s:s + n].reshape(n, 22, 3)
-        return full
-
-    def residual(t):
-        out = torch.empty((F, 17, 3), device=dev)
-        for s, n in chunks:
-            out[s:s + n] = _rel(smplx_model.joints(full_pose(t, s, n), None if b_all is None else b_all[s:s + n],
-                                                   None, None, select="coco"))
-        return (out - target).reshape(F, 51)
-
-    def cost_of(r, t):
-        sq = r.reshape(F, 17, 3).square().sum(2)
-        per = 0.5 * (sq if wj is None else sq * wj).sum(1) + 0.5 * pw * (t - th0).square().sum(1)
-        if F > 1:
-            per[:-1] += 0.5 * sw * tie * (t[1:] - t[:-1]).square().sum(1)
-        return torch.where(live_d, per[pad_d], torch.zeros((), device=dev)).sum(1)
 
     with torch.no_grad():
-        th = th.clone()
-        lam = torch.full((S,), float(lam0), device=dev)
-        jr = torch.empty((F, 51, NUM_DOF), device=dev)
-        r = torch.empty((F, 51), device=dev)
+        fk = _FKView(smplx_model, kps, beta)
         work = torch.empty((lm_chain_workspace_floats(F, NUM_DOF),), device=dev)
-        hist = torch.empty((iters + 1, S), device=dev)
-        cost = cost_of(residual(th), th)
-        hist[0] = cost
-        for it in range(iters):
-            for s, n in chunks:
-                jac, joints = smplx_model.joints_jacobian(full_pose(th, s, n), None if b_all is None else b_all[s:s + n],
-                                                          None, None, select="coco")
-                r[s:s + n] = (_rel(joints) - target[s:s + n]).reshape(n, 51)
-                jr[s:s + n] = _rel(jac.reshape(n, 17, 3, NUM_DOF)).reshape(n, 51, NUM_DOF)
-            delta = lm_solve_chain(jr, r, lam, th, sw, mu=pw, prior=(th - th0).contiguous(), row_weight=row_w,
-                                   seq_starts=starts_d, workspace=work)
-            cand = th + delta
-            cc = cost_of(residual(cand), cand)
-            ok = cc < cost   # False for a NaN step
-            th = torch.where(ok[seg][:, None], cand, th)
-            cost = torch.where(ok, cc, cost)
-            lam = torch.where(ok, lam / 3.0, lam * 3.0)
-            hist[it + 1] = cost
+
+        def cost_of(t):
+            per = _data_term(fk.residual(t), wj) + 0.5 * pw * (t - th0).square().sum(1)
+            if F > 1:
+                per[:-1] += 0.5 * sw * tie * (t[1:] - t[:-1]).square().sum(1)
+            return torch.where(live_d, per[pad_d], torch.zeros((), device=dev)).sum(1)
+
+        def step(t, lam):
+            jr, r = fk.linearize(t)
+            return lm_solve_chain(jr, r, lam, t, sw, mu=pw, prior=(t - th0).contiguous(), row_weight=row_w,
+                                  seq_starts=starts_d, workspace=work)
+
+        lam = torch.full((S,), float(lam0), device=dev)
+        th, hist = _lm_loop(th, cost_of(th), lam, iters, step, cost_of, lambda ok: ok[seg])
     return {"poses": th.cpu().numpy(), "cost": hist.cpu().numpy()}
-
-
-def _sequence_tensors(poses, seq_3d_kps, joint_weight, dev):
-    th = torch.as_tensor(np.ascontiguousarray(np.asarray(poses, dtype=np.float32)[:, :NUM_DOF]), device=dev)
-    F = th.shape[0]
-    kps = torch.as_tensor(np.ascontiguousarray(seq_3d_kps, dtype=np.float32), device=dev).reshape(F, 17, 3)
-    wj = None if joint_weight is None else torch.as_tensor(np.asarray(joint_weight, np.float32), device=dev)
-    return th, kps, wj
-
-
-def _data_term(th, kps, smplx_model, beta, wj):
-    """1/2 sum_f sum_k w_k |r_fk|^2 of the whole sequence at one beta (nb,) device tensor -> 0-d tensor."""
-    from .inference import MAX_WINDOWS_PER_CALL
-    F = th.shape[0]
-    tot = torch.zeros((), device=th.device)
-    for s in range(0, F, MAX_WINDOWS_PER_CALL):
-        n = min(MAX_WINDOWS_PER_CALL, F - s)
-        full = torch.zeros((n, 55, 3), device=th.device)
-        full[:, :22] = th[s:s + n].reshape(n, 22, 3)
-        r = _rel(smplx_model.joints(full, beta[None].expand(n, -1).contiguous(), None, None, select="coco")) - _rel(kps[s:s + n])
-        sq = r.square().sum(2)
-        tot = tot + 0.5 * (sq if wj is None else sq * wj).sum()
-    return tot
 
 
 def fit_shape(poses, seq_3d_kps, smplx_model, betas=None, shape_weight: float = 1e-3, joint_weight=None) -> dict:
@@ -337,37 +392,37 @@ def fit_shape(poses, seq_3d_kps, smplx_model, betas=None, shape_weight: float = 
     affine in beta, so the minimiser does not depend on where the step starts.
     Frames go through in chunks of at most inference.MAX_WINDOWS_PER_CALL, each
     into its own rows of one buffer of partial sums (lm_accumulate), solved
-    once (lm_solve_sum with mu = shape_weight and prior = beta). A step that is
-    NaN is returned as it is; refine_sequence rejects it."""
-    _check_args(poses, seq_3d_kps, 0, 1.0, joint_weight, 1.0)
+    once (lm_solve_sum with mu = shape_weight and prior = beta); the data term
+    is summed chunk by chunk too. A step that is NaN is returned as it is;
+    refine_sequence rejects it."""
+    F = _check_frames(poses, seq_3d_kps)
+    w = _check_joint_weight(joint_weight)
     _check_shape_args(smplx_model, betas, shape_weight)
-    from .inference import MAX_WINDOWS_PER_CALL
-    dev = smplx_model.device
     sw = float(shape_weight)
     nb = smplx_model.num_betas
-    th, kps, wj = _sequence_tensors(poses, seq_3d_kps, joint_weight, dev)
-    F = th.shape[0]
+    th, _, kps, beta = _upload(smplx_model, poses, seq_3d_kps, betas=betas)
+    dev = th.device
+    wj = None if w is None else torch.as_tensor(w, device=dev)
     row_w = None if wj is None else wj.repeat_interleave(3).contiguous()
-    beta = torch.zeros((nb,), device=dev) if betas is None else torch.as_tensor(np.asarray(betas, np.float32), device=dev)
+    if beta is None:
+        beta = torch.zeros((nb,), device=dev)
     with torch.no_grad():
-        rows = [(min(MAX_WINDOWS_PER_CALL, F - s) + LM_RUN - 1) // LM_RUN for s in range(0, F, MAX_WINDOWS_PER_CALL)]
+        chunks = _chunks(F)
+        rows = [(n + LM_RUN - 1) // LM_RUN for _, n in chunks]
         partial = torch.empty((sum(rows), lm_partial_width(nb)), device=dev)
-        q = 0
-        data0 = torch.zeros((), device=dev)
-        for c, s in enumerate(range(0, F, MAX_WINDOWS_PER_CALL)):
-            n = min(MAX_WINDOWS_PER_CALL, F - s)
-            full = torch.zeros((n, 55, 3), device=dev)
-            full[:, :22] = th[s:s + n].reshape(n, 22, 3)
-            jac, joints = smplx_model.joints_shape_jacobian(full, beta[None].expand(n, -1).contiguous(), None, None, select="coco")
-            r3 = _rel(joints) - _rel(kps[s:s + n])
-            sq = r3.square().sum(2)
-            data0 = data0 + 0.5 * (sq if wj is None else sq * wj).sum()
-            jr = _rel(jac.reshape(n, 17, 3, nb)).reshape(n, 51, nb).contiguous()
-            lm_accumulate(jr, r3.reshape(n, 51).contiguous(), row_weight=row_w, out=partial[q:q + rows[c]])
-            q += rows[c]
+
+        views = [(_FKView(smplx_model, _rows(kps, s, n), beta), _rows(th, s, n)) for s, n in chunks]
+        data0 = data1 = torch.zeros((), device=dev)
+        for (fk, t), out in zip(views, partial.split(rows)):
+            jr, r = fk.linearize_shape(t)
+            lm_accumulate(jr, r, row_weight=row_w, out=out)
+            data0 = data0 + _data_term(r, wj, per_frame=False)
         new = beta + lm_solve_sum(partial, mu=sw, lam=0.0, prior=beta.contiguous(), n=nb)
+        for fk, t in views:
+            fk.set_beta(new)
+            data1 = data1 + _data_term(fk.residual(t), wj, per_frame=False)
         c0 = data0 + 0.5 * sw * beta.square().sum()
-        c1 = _data_term(th, kps, smplx_model, new, wj) + 0.5 * sw * new.square().sum()
+        c1 = data1 + 0.5 * sw * new.square().sum()
     return {"betas": new.cpu().numpy(), "cost": torch.stack([c0, c1]).cpu().numpy()}
 
 
@@ -385,7 +440,9 @@ def refine_sequence(poses, seq_3d_kps, smplx_model, rounds: int = 3, iters: int 
     = zero. rounds=0 returns the inputs. smooth_weight > 0: the pose iterations
     are refine_smooth's (the frames one sequence, 1/2 smooth_weight
     sum_f |theta_{f+1} - theta_f|^2 part of the cost); 0 changes nothing."""
-    _check_args(poses, seq_3d_kps, iters, prior_weight, joint_weight, lam0)
+    _check_frames(poses, seq_3d_kps)
+    _check_lm_scalars(iters, prior_weight, lam0)
+    _check_joint_weight(joint_weight)
     _check_shape_args(smplx_model, betas, shape_weight)
     smooth = float(smooth_weight)
     if not smooth >= 0.0:

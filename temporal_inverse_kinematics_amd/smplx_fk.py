@@ -128,6 +128,37 @@ def resolve_dof(dof):
     return d
 
 
+def _check_f32(**tensors):
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32 tensor")
+
+
+def _check_system(who, jac, r, row_weight, max_n=LM_MAX_N, weight_per_body=False):
+    """The stacked systems the lm_* calls take: jac (B,m,n), r (B,m), row_weight None, (m) or, where
+    allowed, (B,m); B >= 1, m <= LM_MAX_M, n <= max_n; contiguous float32. ValueError otherwise;
+    neither the library nor the device is touched. -> (B, m, n)."""
+    if jac.dim() != 3:
+        raise ValueError(f"jac must be (B, m, n), got {tuple(jac.shape)}")
+    B, m, n = (int(s) for s in jac.shape)
+    if B < 1 or not 1 <= n <= max_n or not 1 <= m <= LM_MAX_M:
+        raise ValueError(f"{who}: need B >= 1, 1 <= m <= {LM_MAX_M}, 1 <= n <= {max_n}; got {(B, m, n)}")
+    if tuple(r.shape) != (B, m):
+        raise ValueError(f"r must be {(B, m)}, got {tuple(r.shape)}")
+    shapes = ((m,), (B, m)) if weight_per_body else ((m,),)
+    if row_weight is not None and tuple(row_weight.shape) not in shapes:
+        raise ValueError(f"row_weight must be {' or '.join(map(str, shapes))}, got {tuple(row_weight.shape)}")
+    _check_f32(jac=jac, r=r, row_weight=row_weight)
+    return B, m, n
+
+
+def _non_negative(name, value) -> float:
+    value = float(value)
+    if not value >= 0.0:
+        raise ValueError(f"{name} must be >= 0, got {value}")
+    return value
+
+
 def lm_solve(jac: torch.Tensor, r: torch.Tensor, lam: torch.Tensor, mu: float = 0.0, prior=None, row_weight=None):
     """One damped least-squares step per body (tik_lm_solve):
     (J^T W J + (mu + lam[b]) I) delta = -(J^T W r + mu prior). jac (B,m,n),
@@ -135,22 +166,12 @@ def lm_solve(jac: torch.Tensor, r: torch.Tensor, lam: torch.Tensor, mu: float = 
     or None (one); contiguous float32 on the device. n <= 165, m <= 768,
     mu >= 0; mu + lam[b] > 0 is the caller's promise (a matrix that is not
     positive gives a NaN row, nothing else). -> delta (B,n)."""
-    if jac.dim() != 3:
-        raise ValueError(f"jac must be (B, m, n), got {tuple(jac.shape)}")
-    B, m, n = (int(s) for s in jac.shape)
-    if B < 1 or not 1 <= n <= LM_MAX_N or not 1 <= m <= LM_MAX_M:
-        raise ValueError(f"lm_solve: need B >= 1, 1 <= m <= {LM_MAX_M}, 1 <= n <= {LM_MAX_N}; got {(B, m, n)}")
-    if tuple(r.shape) != (B, m):
-        raise ValueError(f"r must be {(B, m)}, got {tuple(r.shape)}")
+    B, m, n = _check_system("lm_solve", jac, r, row_weight)
     if tuple(lam.shape) != (B,):
         raise ValueError(f"lam must be {(B,)}, got {tuple(lam.shape)}")
     if prior is not None and tuple(prior.shape) != (B, n):
         raise ValueError(f"prior must be {(B, n)}, got {tuple(prior.shape)}")
-    if row_weight is not None and tuple(row_weight.shape) != (m,):
-        raise ValueError(f"row_weight must be {(m,)}, got {tuple(row_weight.shape)}")
-    mu = float(mu)
-    if not mu >= 0.0:
-        raise ValueError(f"mu must be >= 0, got {mu}")
+    mu = _non_negative("mu", mu)
     _lib.require_gpu(jac, r, lam, prior, row_weight)
     delta = torch.empty((B, n), device=jac.device, dtype=torch.float32)
     _lib.check(_lib.load().tik_lm_solve(jac.data_ptr(), r.data_ptr(), _lib.ptr(prior), _lib.ptr(row_weight),
@@ -171,18 +192,7 @@ def lm_accumulate(jac: torch.Tensor, r: torch.Tensor, row_weight=None, out=None)
     then sum_b J_b^T W r_b, over bodies LM_RUN q .. LM_RUN q + LM_RUN - 1. out:
     optional preallocated contiguous float32 tensor of that shape (a slice of
     the buffer a sequence of several chunks accumulates into)."""
-    if jac.dim() != 3:
-        raise ValueError(f"jac must be (B, m, n), got {tuple(jac.shape)}")
-    B, m, n = (int(s) for s in jac.shape)
-    if B < 1 or not 1 <= n <= LM_MAX_N or not 1 <= m <= LM_MAX_M:
-        raise ValueError(f"lm_accumulate: need B >= 1, 1 <= m <= {LM_MAX_M}, 1 <= n <= {LM_MAX_N}; got {(B, m, n)}")
-    if tuple(r.shape) != (B, m):
-        raise ValueError(f"r must be {(B, m)}, got {tuple(r.shape)}")
-    if row_weight is not None and tuple(row_weight.shape) != (m,):
-        raise ValueError(f"row_weight must be {(m,)}, got {tuple(row_weight.shape)}")
-    for name, t in (("jac", jac), ("r", r), ("row_weight", row_weight)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous float32 tensor")
+    B, m, n = _check_system("lm_accumulate", jac, r, row_weight)
     shape = ((B + LM_RUN - 1) // LM_RUN, lm_partial_width(n))
     if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous float32 {shape} tensor")
@@ -214,11 +224,7 @@ def lm_solve_sum(partial: torch.Tensor, mu: float = 0.0, lam: float = 0.0, prior
         raise ValueError("partial must be a contiguous float32 tensor")
     if prior is not None and (tuple(prior.shape) != (n,) or prior.dtype != torch.float32 or not prior.is_contiguous()):
         raise ValueError(f"prior must be a contiguous float32 {(n,)} tensor, got {tuple(prior.shape)}")
-    mu, lam = float(mu), float(lam)
-    if not mu >= 0.0:
-        raise ValueError(f"mu must be >= 0, got {mu}")
-    if not lam >= 0.0:
-        raise ValueError(f"lam must be >= 0, got {lam}")
+    mu, lam = _non_negative("mu", mu), _non_negative("lam", lam)
     _lib.require_gpu(partial, prior)
     delta = torch.empty((n,), device=partial.device, dtype=torch.float32)
     _lib.check(_lib.load().tik_lm_solve_sum(partial.data_ptr(), int(partial.shape[0]), _lib.ptr(prior), mu, lam, n,
@@ -275,13 +281,7 @@ def lm_solve_chain(jac: torch.Tensor, r: torch.Tensor, lam: torch.Tensor, theta,
     elements; it holds the factors afterwards. n <= 96, m <= 768, mu >= 0,
     smooth >= 0; mu + lam[q] > 0 is the caller's promise (a matrix that is not
     positive gives NaN for the whole sequence, nothing else). -> delta (F,n)."""
-    if jac.dim() != 3:
-        raise ValueError(f"jac must be (F, m, n), got {tuple(jac.shape)}")
-    F, m, n = (int(s) for s in jac.shape)
-    if F < 1 or not 1 <= n <= LM_CHAIN_MAX_N or not 1 <= m <= LM_MAX_M:
-        raise ValueError(f"lm_solve_chain: need F >= 1, 1 <= m <= {LM_MAX_M}, 1 <= n <= {LM_CHAIN_MAX_N}; got {(F, m, n)}")
-    if tuple(r.shape) != (F, m):
-        raise ValueError(f"r must be {(F, m)}, got {tuple(r.shape)}")
+    F, m, n = _check_system("lm_solve_chain", jac, r, row_weight, max_n=LM_CHAIN_MAX_N, weight_per_body=True)
     if isinstance(seq_starts, torch.Tensor) and seq_starts.is_cuda:
         starts = seq_starts
         if starts.dtype != torch.int32 or starts.dim() != 1 or not 2 <= starts.shape[0] <= F + 1 or not starts.is_contiguous():
@@ -291,23 +291,14 @@ def lm_solve_chain(jac: torch.Tensor, r: torch.Tensor, lam: torch.Tensor, theta,
     S = int(starts.shape[0]) - 1
     if tuple(lam.shape) != (S,):
         raise ValueError(f"lam must be {(S,)}, one value per sequence, got {tuple(lam.shape)}")
-    mu, smooth = float(mu), float(smooth)
-    if not mu >= 0.0:
-        raise ValueError(f"mu must be >= 0, got {mu}")
-    if not smooth >= 0.0:
-        raise ValueError(f"smooth must be >= 0, got {smooth}")
+    mu, smooth = _non_negative("mu", mu), _non_negative("smooth", smooth)
     if theta is None and smooth != 0.0:
         raise ValueError("theta may be None only with smooth == 0")
     if theta is not None and tuple(theta.shape) != (F, n):
         raise ValueError(f"theta must be {(F, n)}, got {tuple(theta.shape)}")
     if prior is not None and tuple(prior.shape) != (F, n):
         raise ValueError(f"prior must be {(F, n)}, got {tuple(prior.shape)}")
-    if row_weight is not None and tuple(row_weight.shape) not in ((m,), (F, m)):
-        raise ValueError(f"row_weight must be {(m,)} or {(F, m)}, got {tuple(row_weight.shape)}")
-    for name, t in (("jac", jac), ("r", r), ("lam", lam), ("theta", theta), ("prior", prior), ("row_weight", row_weight),
-                    ("workspace", workspace)):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous float32 tensor")
+    _check_f32(lam=lam, theta=theta, prior=prior, workspace=workspace)
     need = lm_chain_workspace_floats(F, n)
     if workspace is not None and workspace.numel() < need:
         raise ValueError(f"workspace must hold at least {need} floats, got {workspace.numel()}")
@@ -380,15 +371,33 @@ class SMPLX:
             raise RuntimeError("the SMPL-X FK runs on the GPU only (no CPU fallback)")
         return self
 
+    @staticmethod
+    def _inputs(full_pose, betas, expression, transl):
+        """-> (full_pose as contiguous (B,55,3), B, [betas, expression, transl] contiguous or None);
+        RuntimeError unless all are on the GPU."""
+        fp = full_pose.reshape(-1, 55, 3).contiguous()
+        args = [t.contiguous() if t is not None else None for t in (betas, expression, transl)]
+        _lib.require_gpu(fp, *args)
+        return fp, fp.shape[0], args
+
+    def _select_with_jacobian(self, select, none_refusal: str, contour_refusal: str):
+        """A selection of joints below num_static_joints -> (indices, their ctypes array). ValueError
+        for None and for a contour landmark, in the calling method's words; the library is not touched."""
+        if select is None:
+            raise ValueError(none_refusal)
+        sel = resolve_select(select, self.num_joints)
+        for j in sel:
+            if j >= self.num_static_joints:
+                raise ValueError(f"joint {j} is a contour landmark {contour_refusal}; "
+                                 f"select joints below {self.num_static_joints}")
+        return sel, (_lib.ctypes.c_int * len(sel))(*sel)
+
     def full_forward(self, full_pose: torch.Tensor, betas=None, expression=None, transl=None,
                      return_verts: bool = True, out=None):
         """full_pose (B,55,3) device -> (joints (B,J,3), vertices (B,V,3) or None).
         out: optional preallocated (joints, vertices) float32 tensors of those
         shapes to write into (a serving loop's output buffers; vertices may be None)."""
-        fp = full_pose.reshape(-1, 55, 3).contiguous()
-        B = fp.shape[0]
-        args = [t.contiguous() if t is not None else None for t in (betas, expression, transl)]
-        _lib.require_gpu(fp, *args)
+        fp, B, args = self._inputs(full_pose, betas, expression, transl)
         if out is not None:
             joints, verts = out
             if joints.shape != (B, self.num_joints, 3) or not joints.is_contiguous() or joints.dtype != torch.float32:
@@ -417,10 +426,7 @@ class SMPLX:
         most 256, duplicates allowed), the output columns in that order. Joints
         below 55 are bit for bit full_forward's, the others within 2e-4 of them.
         out: optional preallocated contiguous float32 (B,n,3) tensor."""
-        fp = full_pose.reshape(-1, 55, 3).contiguous()
-        B = fp.shape[0]
-        args = [t.contiguous() if t is not None else None for t in (betas, expression, transl)]
-        _lib.require_gpu(fp, *args)
+        fp, B, args = self._inputs(full_pose, betas, expression, transl)
         sel = resolve_select(select, self.num_joints)
         n = self.num_joints if sel is None else len(sel)
         if out is not None:
@@ -444,23 +450,15 @@ class SMPLX:
         landmark's vertices change with the pose by bins: no Jacobian; None is not
         allowed). dof: None (joints 0..21) or distinct pose joints in [0, 55).
         joints, when asked for, are bit for bit those of joints(select=select)."""
-        if select is None:
-            raise ValueError("joints_jacobian needs a selection ('coco' or joint indices); "
-                             "all joints would include the contour landmarks, which have no Jacobian")
-        sel = resolve_select(select, self.num_joints)
-        for j in sel:
-            if j >= self.num_static_joints:
-                raise ValueError(f"joint {j} is a contour landmark (its vertices are picked by a pose-dependent bin): "
-                                 f"no Jacobian; select joints below {self.num_static_joints}")
+        sel, csel = self._select_with_jacobian(
+            select, "joints_jacobian needs a selection ('coco' or joint indices); "
+                    "all joints would include the contour landmarks, which have no Jacobian",
+            "(its vertices are picked by a pose-dependent bin): no Jacobian")
         d = resolve_dof(dof)
-        fp = full_pose.reshape(-1, 55, 3).contiguous()
-        B = fp.shape[0]
-        args = [t.contiguous() if t is not None else None for t in (betas, expression, transl)]
-        _lib.require_gpu(fp, *args)
+        fp, B, args = self._inputs(full_pose, betas, expression, transl)
         n, k = len(sel), len(d)
         jac = torch.empty((B, 3 * n, 3 * k), device=fp.device, dtype=torch.float32)
         joints = torch.empty((B, n, 3), device=fp.device, dtype=torch.float32) if return_joints else None
-        csel = (_lib.ctypes.c_int * n)(*sel)
         cdof = None if dof is None else (_lib.ctypes.c_int * k)(*d)
         _lib.check(_lib.load().tik_fk_joints_jacobian(self._h, fp.data_ptr(), _lib.ptr(args[0]), _lib.ptr(args[1]),
                                                       _lib.ptr(args[2]), B, csel, n, cdof, k, jac.data_ptr(),
@@ -478,22 +476,14 @@ class SMPLX:
         num_static_joints (a contour landmark needs the dynamic tables, which
         this call does not read; None is not allowed). joints, when asked for,
         are bit for bit those of joints(select=select)."""
-        if select is None:
-            raise ValueError("joints_shape_jacobian needs a selection ('coco' or joint indices); "
-                             "all joints would include the contour landmarks, which are not supported here")
-        sel = resolve_select(select, self.num_joints)
-        for j in sel:
-            if j >= self.num_static_joints:
-                raise ValueError(f"joint {j} is a contour landmark (its vertices are picked by a pose-dependent bin, from "
-                                 f"tables this call does not read); select joints below {self.num_static_joints}")
-        fp = full_pose.reshape(-1, 55, 3).contiguous()
-        B = fp.shape[0]
-        args = [t.contiguous() if t is not None else None for t in (betas, expression, transl)]
-        _lib.require_gpu(fp, *args)
+        sel, csel = self._select_with_jacobian(
+            select, "joints_shape_jacobian needs a selection ('coco' or joint indices); "
+                    "all joints would include the contour landmarks, which are not supported here",
+            "(its vertices are picked by a pose-dependent bin, from tables this call does not read)")
+        fp, B, args = self._inputs(full_pose, betas, expression, transl)
         n = len(sel)
         jac = torch.empty((B, 3 * n, self.num_betas), device=fp.device, dtype=torch.float32)
         joints = torch.empty((B, n, 3), device=fp.device, dtype=torch.float32) if return_joints else None
-        csel = (_lib.ctypes.c_int * n)(*sel)
         _lib.check(_lib.load().tik_fk_joints_shape_jacobian(self._h, fp.data_ptr(), _lib.ptr(args[0]), _lib.ptr(args[1]),
                                                             _lib.ptr(args[2]), B, csel, n, jac.data_ptr(),
                                                             _lib.ptr(joints), _lib.stream_of(fp)),

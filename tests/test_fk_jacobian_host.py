@@ -57,7 +57,10 @@ def test_lm_solve_validates_before_the_library(no_library):
     J, r, lam = torch.zeros((2, 5, 4)), torch.zeros((2, 5)), torch.ones(2)
     bad = [dict(jac=J[0]), dict(r=r[:, :4]), dict(lam=lam[:1]), dict(mu=-0.5), dict(mu=float("nan")),
            dict(prior=torch.zeros((2, 5))), dict(row_weight=torch.zeros(4)), dict(jac=torch.zeros((2, 5, 166))),
-           dict(jac=torch.zeros((2, 769, 4)), r=torch.zeros((2, 769))), dict(jac=torch.zeros((0, 5, 4)))]
+           dict(jac=torch.zeros((2, 769, 4)), r=torch.zeros((2, 769))), dict(jac=torch.zeros((0, 5, 4))),
+           # not float32, not contiguous: refused as lm_accumulate and lm_solve_chain refuse them, before the device is asked for
+           dict(jac=J.double()), dict(r=r.double()), dict(jac=torch.zeros((2, 5, 8))[:, :, ::2]),
+           dict(row_weight=torch.zeros(5, dtype=torch.float64)), dict(row_weight=torch.zeros((2, 5)))]
     for kw in bad:
         a = dict(jac=J, r=r, lam=lam)
         a.update(kw)
@@ -72,13 +75,17 @@ def test_refine_poses_validates_before_the_library(no_library):
     m = _bare_model()
     poses, kps = np.zeros((3, 66), np.float32), np.zeros((3, 17, 3), np.float32)
     for kw in (dict(prior_weight=0), dict(prior_weight=-1e-3), dict(prior_weight=float("nan")), dict(iters=-1),
-               dict(lam0=0.0), dict(joint_weight=np.ones(16)), dict(joint_weight=-np.ones(17))):
+               dict(lam0=0.0), dict(joint_weight=np.ones(16)), dict(joint_weight=-np.ones(17)),
+               dict(joint_weight=np.ones((3, 17))), dict(joint_weight=np.ones((1, 17))), dict(lam0=float("nan"))):
         with pytest.raises(ValueError):
             refine_poses(poses, kps, m, **kw)
     with pytest.raises(ValueError):
         refine_poses(poses[:, :60], kps, m)
     with pytest.raises(ValueError):
         refine_poses(poses, kps[:2], m)
+    for bad in (poses[0], poses[None], np.zeros((0, 66), np.float32)):      # not (F, >= 66) beside (3,17,3) keypoints
+        with pytest.raises(ValueError):
+            refine_poses(bad, kps, m)
 
 
 def test_refine_argument_parses(no_library):

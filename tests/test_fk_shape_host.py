@@ -82,7 +82,8 @@ def test_fit_shape_and_refine_sequence_validate_before_the_library(no_library):
     m = _bare_model()
     poses, kps = np.zeros((3, 66), np.float32), np.zeros((3, 17, 3), np.float32)
     for kw in (dict(shape_weight=0), dict(shape_weight=0.0), dict(shape_weight=-1e-3), dict(shape_weight=float("nan")),
-               dict(joint_weight=np.ones(16)), dict(joint_weight=-np.ones(17)), dict(betas=np.zeros(9)),
+               dict(joint_weight=np.ones(16)), dict(joint_weight=-np.ones(17)), dict(joint_weight=np.ones((3, 17))),
+               dict(joint_weight=np.full(17, np.nan)), dict(betas=np.zeros(9)),
                dict(betas=np.zeros((1, 10))), dict(betas=np.full(10, np.nan))):
         with pytest.raises(ValueError):
             fit_shape(poses, kps, m, **kw)
@@ -98,6 +99,8 @@ def test_fit_shape_and_refine_sequence_validate_before_the_library(no_library):
             fn(poses[:, :60], kps, m)
         with pytest.raises(ValueError):
             fn(poses, kps[:2], m)
+        with pytest.raises(ValueError):
+            fn(poses[0], kps, m)
     for bad in (poses[:2], poses[:, :60], poses[0]):
         with pytest.raises(ValueError, match="prior_poses"):
             refine_poses(poses, kps, m, prior_poses=bad)

@@ -90,6 +90,7 @@ def test_refine_smooth_validates_before_the_library(no_library):
             refine_smooth(poses, kps, m, sw)
     for kw in (dict(joint_weight=np.ones(16)), dict(joint_weight=np.ones((F + 1, 17))), dict(joint_weight=np.ones((F, 16))),
                dict(joint_weight=np.ones((17, F))), dict(joint_weight=-np.ones(17)), dict(joint_weight=-np.ones((F, 17))),
+               dict(joint_weight=np.ones((1, 17))), dict(joint_weight=np.full((F, 17), np.nan)),
                dict(iters=-1), dict(prior_weight=0), dict(prior_weight=float("nan")), dict(lam0=0.0),
                dict(prior_poses=poses[:2]), dict(seq_starts=[0, 2]), dict(seq_starts=[1, F]), dict(seq_starts=[0, 2, 2, F]),
                dict(seq_starts=[0.0, 3.0])):
@@ -99,6 +100,8 @@ def test_refine_smooth_validates_before_the_library(no_library):
         refine_smooth(poses[:, :60], kps, m, 0.1)
     with pytest.raises(ValueError):
         refine_smooth(poses, kps[:2], m, 0.1)
+    with pytest.raises(ValueError):
+        refine_smooth(poses[0], kps, m, 0.1)
     with pytest.raises(TypeError):
         refine_smooth(poses, kps, m)            # smooth_weight has no default
     for sw in (-0.1, float("nan")):
