@@ -65,28 +65,33 @@ hipError_t launch_fk_landmarks(const FkLmkArgs& a, hipStream_t st);
 //   v_posed[c] = sum_k feat[b][k] PT[3v+c][k]
 //   T = sum_j W[v][j] A_j(b)                             joints ascending (nzw entries, or all 55 of WT)
 //   x = T[:3,:3] v_posed + T[:,3];  joint = sum_i bary_i x_i + transl
-// one lane per body. The k sum is eight 64-k partial sums, each from zero and
-// ascending, added in order; the order of every sum is the same for any B,
-// body position and selection.
+// one lane per body; fk_joints.hip states the order of every sum.
 constexpr int FKJ_MAX_SEL = 256;
 constexpr int FKJ_TB = 64;   // bodies per workgroup tile (lane = body)
-struct FkJointsArgs {
-    int B, n_out, nextra, nlmk, ndyn, nz, sel_all;   // nz: nzw entries per vertex (4, 8, 16) or 0 = dense WT
-    int split;               // set by the launcher: workgroup per column, wave = 64-k chunk (small launches)
-    const float* feat;       // (B,512)
+constexpr int FK_KP = 512;   // feature row length (fk_fold.h KP; asserted in fk_forward.cpp)
+constexpr int FK_SD0 = 486;  // first shape column of a P^T row
+// What the three mesh-free kernels (fk_joints.hip, fk_jacobian.hip, fk_shape.hip) all take, and fk_dev.h works on.
+// nextra: joints 55 .. 55 + nextra are one vertex, later ones three; nz: nzw entries per vertex (4, 8, 16) or 0 = dense WT
+struct FkSelArgs {
+    int B, n_sel, nextra, nz;
     const float* ajt;        // (55,B,12)
-    const float* jchain;     // (B,55,3) chain joints, transl included
-    const float* transl;     // (B,3) or null
-    const float* PT;         // [3V][512]
+    const float* PT;         // [3V][512]: shapedirs[v][c][i] at row 3 v + c, column 486 + i
     const float* WT;         // [V][64]
     const int2* nzw;         // (V,nz) or null
     const int* pick_v;       // (nextra+nlmk, 3) vertex ids of the static joints 55.. (a vertex joint uses entry 0)
     const float* pick_w;     // (nextra+nlmk, 3) their barycentric weights (vertex joint: 1, 0, 0)
+    unsigned short sel[FKJ_MAX_SEL];   // output column s is joint sel[s]
+};
+struct FkJointsArgs : FkSelArgs {   // n_sel: the output columns, all njoints of them when sel_all (sel unused)
+    int nlmk, ndyn, sel_all;
+    int split;               // set by the launcher: workgroup per column, wave = 64-k chunk (small launches)
+    const float* feat;       // (B,512)
+    const float* jchain;     // (B,55,3) chain joints, transl included
+    const float* transl;     // (B,3) or null
     const int* dyn_v;        // (79, ndyn, 3) contour vertex ids by bin
     const float* dyn_w;      // (79, ndyn, 3)
     const int* dyn_bin;      // (B)
-    float* out;              // (B, n_out, 3)
-    unsigned short sel[FKJ_MAX_SEL];
+    float* out;              // (B, n_sel, 3)
 };
 hipError_t launch_fk_joints(const FkJointsArgs& a, hipStream_t st);
 
@@ -101,24 +106,17 @@ hipError_t launch_fk_joints(const FkJointsArgs& a, hipStream_t st);
 // jw[(d * FKJAC_PER_DOF + q) * B + b], q < 27 dR_a[m] (9 a + m), 27 <= q < 36 omega_a[c] (27 + 3 a + c).
 constexpr int FKJAC_PER_DOF = 36;
 constexpr int FKJAC_WS = 55 * FKJAC_PER_DOF;   // floats of jw per body (include/tik.h: 1337 + 1980)
-struct FkJacArgs {
-    int B, n_sel, n_dof, nextra, nz;   // nextra: joints 55 .. 55 + nextra are one vertex, later ones three; nz as FkJointsArgs
+struct FkJacArgs : FkSelArgs {
+    int n_dof;
     const float* pose;       // (B,55,3)
     const float* pose_mean;  // (55,3)
     const int* parents;      // (55)
     const unsigned long long* anc;   // (55) bit j of anc[k]: j is k or an ancestor of k
     const float* feat;       // (B,512)
-    const float* ajt;        // (55,B,12)
     const float* jchain;     // (B,55,3), transl included
     const float* transl;     // (B,3) or null
-    const float* PT;         // [3V][512]
-    const float* WT;         // [V][64]
-    const int2* nzw;         // (V,nz) or null
-    const int* pick_v;       // as FkJointsArgs
-    const float* pick_w;
     float* jw;               // (n_dof, FKJAC_PER_DOF, B)
     float* jac;              // (B, 3 n_sel, 3 n_dof)
-    unsigned short sel[FKJ_MAX_SEL];
     unsigned char dof[56];
 };
 hipError_t launch_fk_jacobian(const FkJacArgs& a, hipStream_t st);
@@ -134,19 +132,12 @@ hipError_t launch_fk_jacobian(const FkJacArgs& a, hipStream_t st);
 // at sw[((i * 55 + k) * 3 + c) * B + b].
 constexpr int FKS_MAX_NB = 25;        // nb + ne <= 25 by the 512-wide feature row
 constexpr int FKS_PER_BETA = 55 * 3;  // floats of sw per body and beta (include/tik.h: 1337 + 165 nb)
-struct FkShapeArgs {
-    int B, n_sel, nb, ns, nextra, nz;  // ns = nb + ne: row length of jd; nextra, nz as FkJacArgs
+struct FkShapeArgs : FkSelArgs {
+    int nb, ns;              // ns = nb + ne: row length of jd
     const int* parents;      // (55), parents[k] < k
     const float* jd;         // (55,3,ns)  J_regressor . [shapedirs | exprdirs]
-    const float* ajt;        // (55,B,12)
-    const float* PT;         // [3V][512]: shapedirs[v][c][i] at row 3 v + c, column 486 + i
-    const float* WT;         // [V][64]
-    const int2* nzw;         // (V,nz) or null
-    const int* pick_v;       // as FkJointsArgs
-    const float* pick_w;
     float* sw;               // (nb, 55, 3, B)
     float* jac;              // (B, 3 n_sel, nb)
-    unsigned short sel[FKJ_MAX_SEL];
 };
 hipError_t launch_fk_shape_jacobian(const FkShapeArgs& a, hipStream_t st);
 

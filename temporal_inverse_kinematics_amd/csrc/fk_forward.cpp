@@ -37,6 +37,7 @@
 #include "xgemm.h"
 
 using namespace tik_host;
+static_assert(KP == tik::FK_KP, "the kernels' feature row is the folded one");
 
 namespace {
 
@@ -105,6 +106,26 @@ int resolve_selection(const tik_fk* fk, const char* who, const int* sel, int n, 
         if (sel) out[s] = (unsigned short)j;
         npick += j < NJ ? 0 : j < NJ + fk->nextra ? 1 : 3;
     }
+    return TIK_OK;
+}
+
+// The arguments the three mesh-free kernels share, from the handle (after its workspace is reserved; sel is set).
+void fill_sel_args(const tik_fk* fk, int B, int n_sel, tik::FkSelArgs& k) {
+    k.B = B; k.n_sel = n_sel; k.nextra = fk->nextra; k.nz = fk->dense ? 0 : fk->sp_nz;
+    k.ajt = fk->ajt.p; k.PT = fk->PT.p; k.WT = fk->WT.p; k.nzw = reinterpret_cast<const int2*>(fk->nzw.p);
+    k.pick_v = fk->pick_v.p; k.pick_w = fk->pick_w.p;
+}
+
+// The two Jacobian entry points between their checks and their own kernels: the joints first, on tik_fk_joints itself
+// (its bits, its "fk_chain" / "fk_joints" launches); the workspace, its 1337 floats per body + the entry point's own
+// (include/tik.h); the chain with feat and A_j forced on unless tik_fk_joints ran it so (npick > 0); then k's base.
+int jacobian_inputs(tik_fk* fk, const FkInputs& in, const int* sel, int n_sel, int npick, float* joints, DevBuf& own,
+                    size_t own_floats, tik::FkSelArgs& k, hipStream_t st) {
+    int rc;
+    if (joints && (rc = tik_fk_joints(fk, in.pose, in.betas, in.expr, in.transl, in.B, sel, n_sel, joints, st))) return rc;
+    if ((rc = reserve_joints_ws(fk, in.B, true)) || (rc = own.reserve(in.B * own_floats))) return rc;
+    if ((!joints || npick == 0) && (rc = launch_chain_joints(fk, in, true, st))) return rc;
+    fill_sel_args(fk, in.B, n_sel, k);
     return TIK_OK;
 }
 
@@ -256,23 +277,20 @@ int tik_fk_joints(tik_fk_t fk, const float* full_pose, const float* betas, const
     hipStream_t st = (hipStream_t)stream;
     tik::FkJointsArgs k{};   // the selection travels in the kernel arguments: nothing is uploaded per call
     k.sel_all = sel_host ? 0 : 1;
-    k.n_out = sel_host ? n_sel : fk->njoints;
+    const int n_out = sel_host ? n_sel : fk->njoints;
     int rc, npick;           // vertex evaluations of this selection
-    if ((rc = resolve_selection(fk, "tik_fk_joints", sel_host, k.n_out, false, k.sel, npick)) ||
+    if ((rc = resolve_selection(fk, "tik_fk_joints", sel_host, n_out, false, k.sel, npick)) ||
         (rc = reserve_joints_ws(fk, B, npick > 0)) ||
         (rc = launch_chain_joints(fk, FkInputs{full_pose, betas, expression, transl, B}, npick > 0, st)))
         return rc;
-    k.B = B; k.nextra = fk->nextra; k.nlmk = fk->nlmk; k.ndyn = fk->ndyn;
-    k.nz = fk->dense ? 0 : fk->sp_nz;
-    k.feat = fk->feat.p; k.ajt = fk->ajt.p; k.jchain = fk->jchain.p; k.transl = transl;
-    k.PT = fk->PT.p; k.WT = fk->WT.p; k.nzw = reinterpret_cast<const int2*>(fk->nzw.p);
-    k.pick_v = fk->pick_v.p; k.pick_w = fk->pick_w.p; k.dyn_v = fk->dyn_v.p; k.dyn_w = fk->dyn_bary.p;
-    k.dyn_bin = fk->dyn_bin.p; k.out = out;
+    fill_sel_args(fk, B, n_out, k);
+    k.nlmk = fk->nlmk; k.ndyn = fk->ndyn; k.feat = fk->feat.p; k.jchain = fk->jchain.p; k.transl = transl;
+    k.dyn_v = fk->dyn_v.p; k.dyn_w = fk->dyn_bary.p; k.dyn_bin = fk->dyn_bin.p; k.out = out;
     // algorithmic, per vertex evaluation: 3 dot products of 507 + the skinning sum + the 3x4 transform;
     // bytes: feat and A_j in, the picked P^T rows once, the joints out
     const double terms = k.nz ? k.nz : NJ;
     ProfRange pr(fk->profiling ? &fk->prof : nullptr, "fk_joints", 2.0 * B * npick * (3.0 * 507 + 12.0 * terms + 9.0),
-                 4.0 * ((double)B * (npick ? KP + 12 * NJ : 0) + 3.0 * 507 * npick + 3.0 * B * NJ + 3.0 * B * k.n_out), st);
+                 4.0 * ((double)B * (npick ? KP + 12 * NJ : 0) + 3.0 * 507 * npick + 3.0 * B * NJ + 3.0 * B * n_out), st);
     HIP_TRY(tik::launch_fk_joints(k, st));
     return TIK_OK;
 }
@@ -298,21 +316,10 @@ int tik_fk_joints_jacobian(tik_fk_t fk, const float* full_pose, const float* bet
         seen |= 1ull << j;
         k.dof[d] = (unsigned char)j;
     }
-    // the joints first, on tik_fk_joints itself (its bits, its "fk_chain" / "fk_joints" launches)
-    if (joints && (rc = tik_fk_joints(fk, full_pose, betas, expression, transl, B, sel_host, n_sel, joints, stream))) return rc;
-    // workspace: tik_fk_joints' 1337 floats per body + FKJAC_WS (include/tik.h)
-    if ((rc = reserve_joints_ws(fk, B, true)) || (rc = fk->jacw.reserve((size_t)B * tik::FKJAC_WS))) return rc;
-    // the chain with the feature and the transforms forced on, unless tik_fk_joints above already ran it
-    // that way (it does when a selected joint is made of vertices)
-    if ((!joints || npick == 0) && (rc = launch_chain_joints(fk, FkInputs{full_pose, betas, expression, transl, B}, true, st)))
-        return rc;
-    k.B = B; k.n_sel = n_sel; k.nextra = fk->nextra;
-    k.nz = fk->dense ? 0 : fk->sp_nz;
+    if ((rc = jacobian_inputs(fk, FkInputs{full_pose, betas, expression, transl, B}, sel_host, n_sel, npick, joints, fk->jacw,
+                              tik::FKJAC_WS, k, st))) return rc;
     k.pose = full_pose; k.pose_mean = fk->pose_mean.p; k.parents = fk->parents.p; k.anc = fk->anc.p;
-    k.feat = fk->feat.p; k.ajt = fk->ajt.p; k.jchain = fk->jchain.p; k.transl = transl;
-    k.PT = fk->PT.p; k.WT = fk->WT.p; k.nzw = reinterpret_cast<const int2*>(fk->nzw.p);
-    k.pick_v = fk->pick_v.p; k.pick_w = fk->pick_w.p;
-    k.jw = fk->jacw.p; k.jac = jac;
+    k.feat = fk->feat.p; k.jchain = fk->jchain.p; k.transl = transl; k.jw = fk->jacw.p; k.jac = jac;
     // algorithmic, per (vertex evaluation, dof): the masked skinning sum, three cross products, the
     // 27-term pose-blend derivative and its 3x3 transform; per vertex evaluation the 3 dot products of
     // 507; bytes: the Jacobian out, feat / A_j / chain joints in, the dof workspace written and read
@@ -336,20 +343,9 @@ int tik_fk_joints_shape_jacobian(tik_fk_t fk, const float* full_pose, const floa
     tik::FkShapeArgs k{};   // the selection travels in the kernel arguments: nothing is uploaded per call
     int rc, npick;
     if ((rc = resolve_selection(fk, "tik_fk_joints_shape_jacobian", sel_host, n_sel, true, k.sel, npick))) return rc;
-    // the joints first, on tik_fk_joints itself (its bits, its "fk_chain" / "fk_joints" launches)
-    if (joints && (rc = tik_fk_joints(fk, full_pose, betas, expression, transl, B, sel_host, n_sel, joints, stream))) return rc;
-    // workspace: tik_fk_joints' 1337 floats per body + 165 nb (include/tik.h)
-    if ((rc = reserve_joints_ws(fk, B, true)) || (rc = fk->shpw.reserve((size_t)B * tik::FKS_PER_BETA * fk->nb))) return rc;
-    // the chain with the transforms forced on, unless tik_fk_joints above already ran it that way (it
-    // does when a selected joint is made of vertices)
-    if ((!joints || npick == 0) && (rc = launch_chain_joints(fk, FkInputs{full_pose, betas, expression, transl, B}, true, st)))
-        return rc;
-    k.B = B; k.n_sel = n_sel; k.nb = fk->nb; k.ns = fk->nb + fk->ne; k.nextra = fk->nextra;
-    k.nz = fk->dense ? 0 : fk->sp_nz;
-    k.parents = fk->parents.p; k.jd = fk->jd.p; k.ajt = fk->ajt.p;
-    k.PT = fk->PT.p; k.WT = fk->WT.p; k.nzw = reinterpret_cast<const int2*>(fk->nzw.p);
-    k.pick_v = fk->pick_v.p; k.pick_w = fk->pick_w.p;
-    k.sw = fk->shpw.p; k.jac = jac;
+    if ((rc = jacobian_inputs(fk, FkInputs{full_pose, betas, expression, transl, B}, sel_host, n_sel, npick, joints, fk->shpw,
+                              (size_t)tik::FKS_PER_BETA * fk->nb, k, st))) return rc;
+    k.nb = fk->nb; k.ns = fk->nb + fk->ne; k.parents = fk->parents.p; k.jd = fk->jd.p; k.sw = fk->shpw.p; k.jac = jac;
     // algorithmic, per (body, beta): the chain's 54 rotated differences; per (vertex evaluation,
     // skinning entry, beta): a 3x3 product, the add of dP and the weighted sum; bytes: the Jacobian
     // out, A_j in, the beta workspace written and read

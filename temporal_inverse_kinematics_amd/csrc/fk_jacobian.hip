@@ -32,23 +32,19 @@
 // a lane works for its own body only, so a body's rows are the same bits for
 // any B, any place in the batch and any selection around the column. A body's
 // row is written in runs of 3 floats, contiguous over 3 n_dof. No atomics, no
-// waiting between workgroups, plain vector stores.
-#include "fk.h"
-#include "dev_common.h"
+// waiting between workgroups, plain vector stores. fk_dev.h (shared with fk_joints.hip and fk_shape.hip) holds
+// the column of a wave, the decode of a static joint's vertices, the rows of A_k and the two row products; the
+// blend dot product stays here (one 512-k chain, not fk_joints_kernel's eight chunks: other bits).
+#include "fk_dev.h"
 
 namespace tik {
-
-namespace fkjac {
-constexpr int TB = FKJ_TB;    // bodies per tile
-constexpr int KP = 512;       // feature row length
+using namespace fkd;   // TB bodies per tile, KP the feature row length
 constexpr int PD = FKJAC_PER_DOF;
-}  // namespace fkjac
 
 __global__ __launch_bounds__(64) void fk_jac_pre_kernel(FkJacArgs a) {
-    using namespace fkjac;
-    const int b = blockIdx.x * TB + threadIdx.x;
-    if (b >= a.B) return;   // no barrier below
-    const int d = blockIdx.y, j = a.dof[d];
+    int b, d;
+    if (!pre_body(a, b, d)) return;   // no barrier below
+    const int j = a.dof[d];
     const float* pz = a.pose + ((size_t)b * 55 + j) * 3;
     const float v[3] = {pz[0] + a.pose_mean[j * 3], pz[1] + a.pose_mean[j * 3 + 1], pz[2] + a.pose_mean[j * 3 + 2]};
     const float u[3] = {v[0] + 1e-8f, v[1] + 1e-8f, v[2] + 1e-8f};
@@ -77,21 +73,16 @@ __global__ __launch_bounds__(64) void fk_jac_pre_kernel(FkJacArgs a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) K2[3 * r + c] = v[r] * v[c] - (r == c ? vv : 0.f);
     float Gp[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, Gj[9];
+    auto rot = [&](int k, float* G) __attribute__((always_inline)) {   // the 3x3 part of A_k
+        const f32x4* r = ak_rows(a, k, b);
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) G[3 * q + c] = r[q][c];
+    };
     const int p = a.parents[j];
-    {
-        const float* g = a.ajt + ((size_t)j * a.B + b) * 12;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Gj[3 * r + c] = g[4 * r + c];
-        if (p >= 0) {
-            const float* q = a.ajt + ((size_t)p * a.B + b) * 12;
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) Gp[3 * r + c] = q[4 * r + c];
-        }
-    }
+    rot(j, Gj);
+    if (p >= 0) rot(p, Gp);
     float* o = a.jw + (size_t)d * PD * a.B + b;
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) {
@@ -114,12 +105,12 @@ __global__ __launch_bounds__(64) void fk_jac_pre_kernel(FkJacArgs a) {
         for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                M[3 * r + c] = fmaf(Gp[3 * r + 2], dR[6 + c], fmaf(Gp[3 * r + 1], dR[3 + c], Gp[3 * r] * dR[c]));
+                M[3 * r + c] = row_linear(Gp[3 * r], Gp[3 * r + 1], Gp[3 * r + 2], dR[c], dR[3 + c], dR[6 + c]);
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                W[3 * r + c] = fmaf(M[3 * r + 2], Gj[3 * c + 2], fmaf(M[3 * r + 1], Gj[3 * c + 1], M[3 * r] * Gj[3 * c]));
+                W[3 * r + c] = row_linear(M[3 * r], M[3 * r + 1], M[3 * r + 2], Gj[3 * c], Gj[3 * c + 1], Gj[3 * c + 2]);
         o[(size_t)(27 + 3 * ax) * a.B] = 0.5f * (W[7] - W[5]);
         o[(size_t)(27 + 3 * ax + 1) * a.B] = 0.5f * (W[2] - W[6]);
         o[(size_t)(27 + 3 * ax + 2) * a.B] = 0.5f * (W[3] - W[1]);
@@ -129,14 +120,10 @@ __global__ __launch_bounds__(64) void fk_jac_pre_kernel(FkJacArgs a) {
 // MAXK: skinning entries per vertex at most (16: the pairs; 55: the dense WT rows); JW: columns (waves) per workgroup
 template <int MAXK, int JW>
 __global__ __launch_bounds__(64 * JW) void fk_jacobian_kernel(FkJacArgs a) {
-    using namespace fkjac;
     __shared__ float sX[JW][MAXK * 3 * 64];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int b = blockIdx.x * TB + lane;
-    const int s = blockIdx.y * JW + wv;
-    if (s >= a.n_sel || b >= a.B) return;   // no barrier in this kernel
-    const int jn = a.sel[s];
+    Column col;
+    if (!column(a, JW, col)) return;   // no barrier in this kernel
+    const int lane = col.lane, b = col.b, s = col.s, jn = col.jn;
     const size_t B = a.B;
     const int nd3 = 3 * a.n_dof;
     float* row = a.jac + ((size_t)b * 3 * a.n_sel + 3 * s) * nd3;   // rows 3 s .. 3 s + 2 of this body
@@ -173,13 +160,11 @@ __global__ __launch_bounds__(64 * JW) void fk_jacobian_kernel(FkJacArgs a) {
     }
 
     // a vertex joint (one vertex) or a static landmark (three)
-    const int jj = jn - 55;
-    const int npick = jj < a.nextra ? 1 : 3;
-    float* X = sX[wv];
-    const int K = a.nz > 0 ? a.nz : 55;
+    const int npick = pick_count(a, jn), K = skin_count(a);
+    float* X = sX[col.wv];
     for (int i = 0; i < npick; ++i) {
-        const int v = __builtin_amdgcn_readfirstlane(a.pick_v[jj * 3 + i]);
-        const float bw = a.pick_w[jj * 3 + i];
+        const Pick pk = pick(a, jn, i);
+        const int v = pk.v;
         // posed blend position vp = feat . P^T rows 3 v .. 3 v + 2, k ascending
         float vp[3] = {0.f, 0.f, 0.f};
         {
@@ -195,44 +180,39 @@ __global__ __launch_bounds__(64 * JW) void fk_jacobian_kernel(FkJacArgs a) {
                 }
             }
         }
-        auto entry = [&](int n, int& k, float& w) __attribute__((always_inline)) {
+        // fk_dev.h's skin_entry<false> and ak_rows, spelled out: through the helpers the compiler contracts the cross
+        // products below another way (other bits)
+        auto entry = [&](int n) __attribute__((always_inline)) -> SkinEntry {
             if (a.nz > 0) {
                 const int2 e = a.nzw[(size_t)v * a.nz + n];
-                k = e.x;
-                w = __builtin_bit_cast(float, e.y);
-            } else {
-                k = n;
-                w = a.WT[(size_t)v * 64 + n];
+                return {e.x, __builtin_bit_cast(float, e.y)};
             }
+            return {n, a.WT[(size_t)v * 64 + n]};
         };
         // x_n = A_k(vp) into the slab, T.R = sum_n w_n A_k.R
         float TR[9];
 #pragma unroll
         for (int e = 0; e < 9; ++e) TR[e] = 0.f;
         for (int n = 0; n < K; ++n) {
-            int k;
-            float w;
-            entry(n, k, w);
-            const f32x4* r = reinterpret_cast<const f32x4*>(a.ajt + ((size_t)k * B + b) * 12);
+            const SkinEntry e = entry(n);
+            const f32x4* r = reinterpret_cast<const f32x4*>(a.ajt + ((size_t)e.k * B + b) * 12);
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 const f32x4 t = r[q];
-                X[(n * 3 + q) * 64 + lane] = fmaf(t[0], vp[0], fmaf(t[1], vp[1], fmaf(t[2], vp[2], t[3])));
+                X[(n * 3 + q) * 64 + lane] = row_affine(t, vp);
 #pragma unroll
-                for (int e = 0; e < 3; ++e) TR[3 * q + e] = fmaf(w, t[e], TR[3 * q + e]);
+                for (int c = 0; c < 3; ++c) TR[3 * q + c] = fmaf(e.w, t[c], TR[3 * q + c]);
             }
         }
         for (int d = 0; d < a.n_dof; ++d) {
             const int j = a.dof[d];
             float S[3] = {0.f, 0.f, 0.f}, sw = 0.f;
             for (int n = 0; n < K; ++n) {
-                int k;
-                float w;
-                entry(n, k, w);
-                if ((a.anc[k] >> j) & 1ull) {
+                const SkinEntry e = entry(n);
+                if ((a.anc[e.k] >> j) & 1ull) {
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) S[c] = fmaf(w, X[(n * 3 + c) * 64 + lane], S[c]);
-                    sw += w;
+                    for (int c = 0; c < 3; ++c) S[c] = fmaf(e.w, X[(n * 3 + c) * 64 + lane], S[c]);
+                    sw += e.w;
                 }
             }
             // the posed joint without the translation, as A_k(vp) is
@@ -256,10 +236,10 @@ __global__ __launch_bounds__(64 * JW) void fk_jacobian_kernel(FkJacArgs a) {
                     }
 #pragma unroll
                     for (int c = 0; c < 3; ++c)
-                        t[c] += fmaf(TR[3 * c + 2], u3[2], fmaf(TR[3 * c + 1], u3[1], TR[3 * c] * u3[0]));
+                        t[c] += row_linear(TR[3 * c], TR[3 * c + 1], TR[3 * c + 2], u3[0], u3[1], u3[2]);
                 }
 #pragma unroll
-                for (int c = 0; c < 3; ++c) o[3 * c + ax] = bw * t[c];
+                for (int c = 0; c < 3; ++c) o[3 * c + ax] = pk.bw * t[c];
             }
 #pragma unroll
             for (int c = 0; c < 3; ++c)
@@ -273,11 +253,10 @@ __global__ __launch_bounds__(64 * JW) void fk_jacobian_kernel(FkJacArgs a) {
 }
 
 hipError_t launch_fk_jacobian(const FkJacArgs& a, hipStream_t st) {
-    if (a.B <= 0 || a.n_sel <= 0 || a.n_sel > FKJ_MAX_SEL || a.n_dof <= 0 || a.n_dof > 55 || !a.jac || !a.jw || !a.anc ||
-        (a.nz != 0 && a.nz != 4 && a.nz != 8 && a.nz != 16) || (a.nz && !a.nzw))
+    if (a.B <= 0 || a.n_sel <= 0 || a.n_sel > FKJ_MAX_SEL || a.n_dof <= 0 || a.n_dof > 55 || !a.jac || !a.jw || !a.anc || !nz_ok(a))
         return hipErrorInvalidValue;
     (void)hipGetLastError();
-    const unsigned tiles = (a.B + fkjac::TB - 1) / fkjac::TB;
+    const unsigned tiles = (a.B + TB - 1) / TB;
     hipLaunchKernelGGL(fk_jac_pre_kernel, dim3(tiles, a.n_dof), dim3(64), 0, st, a);
     if (a.nz > 0) {
         constexpr int JW = 4;

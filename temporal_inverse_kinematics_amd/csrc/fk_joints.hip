@@ -25,27 +25,22 @@
 // LDS by wave 0 in the same order. Both mappings and both regimes give the
 // same bits, so a result does not depend on B, on the body's place in the
 // batch, or on what else is selected. No atomics, no waiting between
-// workgroups.
-#include "fk.h"
-#include "dev_common.h"
+// workgroups. fk_dev.h (shared with fk_jacobian.hip, fk_shape.hip): the walk over a vertex's skinning entries, a
+// static joint's vertices, the rows of A_k, the affine row product; not the dot product above (see there).
+#include "fk_dev.h"
 
 namespace tik {
-
-namespace fkj {
-constexpr int TB = FKJ_TB;           // bodies per tile
-constexpr int JW = 8;                // output columns (waves) per workgroup
-constexpr int KC = 64;               // k per staged chunk
-constexpr int KP = 512;              // feature row length (fk_fold.h KP)
-constexpr int LDF = TB + 1;          // LDS row stride of the transposed chunk (the staging writes spread over banks)
+using namespace fkd;         // TB bodies per tile, KP the feature row length
+constexpr int JW = 8;        // output columns (waves) per workgroup
+constexpr int KC = 64;       // k per staged chunk
+constexpr int LDF = TB + 1;  // LDS row stride of the transposed chunk (the staging writes spread over banks)
 constexpr int NLD = KC * TB / 4 / (64 * JW);   // f32x4 staging loads per thread per chunk
 static_assert(NLD * 4 * 64 * JW == KC * TB, "chunk must divide over the workgroup");
-}  // namespace fkj
 
 // part[3 i + c] = sum over the chunk's k of feat[b][k] * PT[3 v_i + c][k], from zero, k ascending.
 // DIRECT: sf is the lane's own feature row in global memory; else the transposed chunk in LDS.
 template <int NP, bool DIRECT>
 __device__ __forceinline__ void fkj_blend_chunk(float (&part)[9], const float* sf, const float* const (&row)[3], int lane) {
-    using namespace fkj;
 #pragma unroll
     for (int e = 0; e < 9; ++e) part[e] = 0.f;
 #pragma unroll 2
@@ -72,7 +67,6 @@ __device__ __forceinline__ void fkj_blend_chunk(float (&part)[9], const float* s
 template <bool DIRECT>
 __device__ __forceinline__ void fkj_chunk(float (&part)[9], int kind, const float* sf, const float* const (&urow)[3],
                                           const float* const (&lrow)[3], int kc, int lane) {
-    using namespace fkj;
     if (kind == 3) {
         const float* const rk[3] = {lrow[0] + kc * KC, lrow[1] + kc * KC, lrow[2] + kc * KC};
         fkj_blend_chunk<3, DIRECT>(part, sf, rk, lane);
@@ -83,34 +77,27 @@ __device__ __forceinline__ void fkj_chunk(float (&part)[9], int kind, const floa
     }
 }
 
-// x = T[:3,:3] vp + T[:,3] with T = sum_j W[v][j] A_j(b), joints ascending
+// x = T[:3,:3] vp + T[:,3] with T = sum_j W[v][j] A_j(b), the skinning entries in table order (joints ascending)
 __device__ __forceinline__ void fkj_skin(const FkJointsArgs& a, int v, int b, const float* vp, float* x) {
     float T[12];
 #pragma unroll
     for (int e = 0; e < 12; ++e) T[e] = 0.f;
-    auto add = [&](int j, float w) __attribute__((always_inline)) {
-        const f32x4* r = reinterpret_cast<const f32x4*>(a.ajt + ((size_t)j * a.B + b) * 12);
+    const int K = skin_count(a);
+    for (int n = 0; n < K; ++n) {
+        const SkinEntry s = skin_entry<false>(a, v, n);   // v is the lane's own for a contour joint
+        const f32x4* r = ak_rows(a, s.k, b);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             const f32x4 t = r[q];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) T[4 * q + e] = fmaf(w, t[e], T[4 * q + e]);
+            for (int e = 0; e < 4; ++e) T[4 * q + e] = fmaf(s.w, t[e], T[4 * q + e]);
         }
-    };
-    if (a.nz > 0) {   // the pairs of fk_skin_sparse_kernel (W > 2^-30), padding {0, 0.f} included
-        for (int n = 0; n < a.nz; ++n) {
-            const int2 e = a.nzw[(size_t)v * a.nz + n];
-            add(e.x, __builtin_bit_cast(float, e.y));
-        }
-    } else {
-        for (int j = 0; j < 55; ++j) add(j, a.WT[(size_t)v * 64 + j]);
     }
 #pragma unroll
-    for (int g = 0; g < 3; ++g) x[g] = fmaf(T[4 * g], vp[0], fmaf(T[4 * g + 1], vp[1], fmaf(T[4 * g + 2], vp[2], T[4 * g + 3])));
+    for (int g = 0; g < 3; ++g) x[g] = row_affine(f32x4{T[4 * g], T[4 * g + 1], T[4 * g + 2], T[4 * g + 3]}, vp);
 }
 
-__global__ __launch_bounds__(64 * fkj::JW) void fk_joints_kernel(FkJointsArgs a) {
-    using namespace fkj;
+__global__ __launch_bounds__(64 * JW) void fk_joints_kernel(FkJointsArgs a) {
     __shared__ __attribute__((aligned(16))) float sF[2][KC * LDF];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -120,7 +107,7 @@ __global__ __launch_bounds__(64 * fkj::JW) void fk_joints_kernel(FkJointsArgs a)
     // this wave's output column: split, the workgroup's one; else every gridDim.y-th, from blockIdx.y
     const int nby = gridDim.y;
     const int s = a.split ? (int)blockIdx.y : wv * nby + (int)blockIdx.y;
-    auto joint_of = [&](int col) { return col < a.n_out ? (a.sel_all ? col : (int)a.sel[col]) : -1; };
+    auto joint_of = [&](int col) { return col < a.n_sel ? (a.sel_all ? col : (int)a.sel[col]) : -1; };
     const int j = joint_of(s);
     bool need = j >= 55;   // any column of this workgroup past the chain joints
     if (!a.split)
@@ -133,8 +120,9 @@ __global__ __launch_bounds__(64 * fkj::JW) void fk_joints_kernel(FkJointsArgs a)
     float w[3] = {0.f, 0.f, 0.f};
     if (kind == 1 || kind == 2) {
         for (int i = 0; i < 3; ++i) {
-            vu[i] = __builtin_amdgcn_readfirstlane(a.pick_v[jj * 3 + i]);
-            w[i] = a.pick_w[jj * 3 + i];
+            const Pick p = pick(a, j, i);
+            vu[i] = p.v;
+            w[i] = p.bw;
         }
     } else if (kind == 3) {
         const int bin = min(max(a.dyn_bin[bc], 0), 78);
@@ -219,22 +207,20 @@ __global__ __launch_bounds__(64 * fkj::JW) void fk_joints_kernel(FkJointsArgs a)
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[c] += a.transl ? a.transl[(size_t)b * 3 + c] : 0.f;
     }
-    float* d = a.out + ((size_t)b * a.n_out + s) * 3;
+    float* d = a.out + ((size_t)b * a.n_sel + s) * 3;
     d[0] = o[0]; d[1] = o[1]; d[2] = o[2];
 }
 
 hipError_t launch_fk_joints(const FkJointsArgs& a, hipStream_t st) {
-    if (a.B <= 0 || a.n_out <= 0) return hipSuccess;
-    if (!a.jchain || !a.out || (!a.sel_all && a.n_out > FKJ_MAX_SEL) || (a.nz != 0 && a.nz != 4 && a.nz != 8 && a.nz != 16) ||
-        (a.nz && !a.nzw))
-        return hipErrorInvalidValue;
+    if (a.B <= 0 || a.n_sel <= 0) return hipSuccess;
+    if (!a.jchain || !a.out || (!a.sel_all && a.n_sel > FKJ_MAX_SEL) || !nz_ok(a)) return hipErrorInvalidValue;
     (void)hipGetLastError();
     // few workgroups (a small batch or a short selection): a workgroup per column, its waves over k
     FkJointsArgs k = a;
-    const unsigned tiles = (a.B + fkj::TB - 1) / fkj::TB, nby = (a.n_out + fkj::JW - 1) / fkj::JW;
+    const unsigned tiles = (a.B + TB - 1) / TB, nby = (a.n_sel + JW - 1) / JW;
     k.split = tiles * nby <= 64 ? 1 : 0;
-    static_assert(8 * 9 * 64 <= 2 * fkj::KC * fkj::LDF, "the split partials reuse the chunk buffers");
-    hipLaunchKernelGGL(fk_joints_kernel, dim3(tiles, k.split ? a.n_out : nby), dim3(64 * fkj::JW), 0, st, k);
+    static_assert(8 * 9 * 64 <= 2 * KC * LDF, "the split partials reuse the chunk buffers");
+    hipLaunchKernelGGL(fk_joints_kernel, dim3(tiles, k.split ? a.n_sel : nby), dim3(64 * JW), 0, st, k);
     return hipGetLastError();
 }
 

@@ -22,26 +22,19 @@
 // (x 1 for a vertex joint), every term an fp32 FMA chain in that one order; a lane works for its
 // own body only, so a body's rows are the same bits for any B, any place in the batch and any
 // selection around the column. A body's rows 3 s .. 3 s + 2 are one run of 3 nb floats. No atomics,
-// no waiting between workgroups, plain vector stores.
-#include "fk.h"
-#include "dev_common.h"
+// no waiting between workgroups, plain vector stores. fk_dev.h (shared with fk_joints.hip, fk_jacobian.hip): the
+// column of a wave, the skinning entries (here made scalar), a static joint's vertices, the rows of A_k, row_linear.
+#include "fk_dev.h"
 
 namespace tik {
-
-namespace fkshape {
-constexpr int TB = FKJ_TB;        // bodies per tile
-constexpr int KP = 512;           // feature row length
-constexpr int SD0 = 486;          // first shape column of a P^T row
+using namespace fkd;   // TB bodies per tile, KP the feature row length, SD0 the first shape column
 constexpr int MAXNB = FKS_MAX_NB;
 constexpr int PB = FKS_PER_BETA;
-constexpr int JW = 4;             // columns (waves) per workgroup
-}  // namespace fkshape
+constexpr int JW = 4;   // columns (waves) per workgroup
 
 __global__ __launch_bounds__(64) void fk_shape_pre_kernel(FkShapeArgs a) {
-    using namespace fkshape;
-    const int b = blockIdx.x * TB + threadIdx.x;
-    if (b >= a.B) return;   // no barrier below
-    const int i = blockIdx.y;
+    int b, i;
+    if (!pre_body(a, b, i)) return;   // no barrier below
     const size_t B = a.B;
     float* o = a.sw + (size_t)i * PB * B + b;
 #pragma unroll
@@ -51,24 +44,19 @@ __global__ __launch_bounds__(64) void fk_shape_pre_kernel(FkShapeArgs a) {
         const float* jk = a.jd + (size_t)k * 3 * a.ns + i;
         const float* jp = a.jd + (size_t)p * 3 * a.ns + i;
         const float d[3] = {jk[0] - jp[0], jk[a.ns] - jp[a.ns], jk[2 * a.ns] - jp[2 * a.ns]};
-        const f32x4* r = reinterpret_cast<const f32x4*>(a.ajt + ((size_t)p * B + b) * 12);
+        const f32x4* r = ak_rows(a, p, b);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const f32x4 t = r[c];
-            const float rd = fmaf(t[2], d[2], fmaf(t[1], d[1], t[0] * d[0]));
-            o[(size_t)(3 * k + c) * B] = o[(size_t)(3 * p + c) * B] + rd;
+            o[(size_t)(3 * k + c) * B] = o[(size_t)(3 * p + c) * B] + row_linear(t[0], t[1], t[2], d[0], d[1], d[2]);
         }
     }
 }
 
-__global__ __launch_bounds__(64 * fkshape::JW) void fk_shape_jacobian_kernel(FkShapeArgs a) {
-    using namespace fkshape;
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int b = blockIdx.x * TB + lane;
-    const int s = blockIdx.y * JW + wv;
-    if (s >= a.n_sel || b >= a.B) return;   // no barrier in this kernel
-    const int jn = a.sel[s];
+__global__ __launch_bounds__(64 * JW) void fk_shape_jacobian_kernel(FkShapeArgs a) {
+    Column col;
+    if (!column(a, JW, col)) return;   // no barrier in this kernel
+    const int b = col.b, s = col.s, jn = col.jn;
     const size_t B = a.B;
     const int nb = a.nb;
     float* row = a.jac + ((size_t)b * 3 * a.n_sel + 3 * s) * nb;   // rows 3 s .. 3 s + 2 of this body
@@ -81,40 +69,28 @@ __global__ __launch_bounds__(64 * fkshape::JW) void fk_shape_jacobian_kernel(FkS
     }
 
     // a vertex joint (one vertex) or a static landmark (three)
-    const int jj = jn - 55;
-    const int npick = jj < a.nextra ? 1 : 3;
-    const int K = a.nz > 0 ? a.nz : 55;   // skinning entries per vertex: the pairs, or the dense WT row
+    const int npick = pick_count(a, jn), K = skin_count(a);
     float acc[3 * MAXNB];
 #pragma unroll
     for (int e = 0; e < 3 * MAXNB; ++e) acc[e] = 0.f;
     for (int q = 0; q < npick; ++q) {
-        const int v = __builtin_amdgcn_readfirstlane(a.pick_v[jj * 3 + q]);
-        const float bw = a.pick_w[jj * 3 + q];
-        const float* sd = a.PT + (size_t)v * 3 * KP + SD0;
+        const Pick pk = pick(a, jn, q);
+        const float* sd = a.PT + (size_t)pk.v * 3 * KP + SD0;
         for (int n = 0; n < K; ++n) {
-            int k;
-            float w;
-            if (a.nz > 0) {
-                const int2 e = a.nzw[(size_t)v * a.nz + n];
-                k = __builtin_amdgcn_readfirstlane(e.x);   // v is wave-uniform, so is its table row
-                w = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(e.y));
-            } else {
-                k = n;
-                w = a.WT[(size_t)v * 64 + n];
-            }
-            w *= bw;   // a vertex joint: x 1
-            const f32x4* r = reinterpret_cast<const f32x4*>(a.ajt + ((size_t)k * B + b) * 12);
+            const SkinEntry e = skin_entry<true>(a, pk.v, n);   // the vertex is wave-uniform, so is its table row
+            const float w = e.w * pk.bw;   // a vertex joint: x 1
+            const f32x4* r = ak_rows(a, e.k, b);
             const f32x4 r0 = r[0], r1 = r[1], r2 = r[2];
-            const float* jd = a.jd + (size_t)k * 3 * a.ns;
-            const float* dp = a.sw + (size_t)3 * k * B + b;
+            const float* jd = a.jd + (size_t)e.k * 3 * a.ns;
+            const float* dp = a.sw + (size_t)3 * e.k * B + b;
 #pragma unroll
             for (int i = 0; i < MAXNB; ++i) {
                 if (i < nb) {
                     const float d0 = sd[i] - jd[i], d1 = sd[KP + i] - jd[a.ns + i], d2 = sd[2 * KP + i] - jd[2 * a.ns + i];
                     const float* p = dp + (size_t)i * PB * B;
-                    const float u0 = fmaf(r0[2], d2, fmaf(r0[1], d1, r0[0] * d0)) + p[0];
-                    const float u1 = fmaf(r1[2], d2, fmaf(r1[1], d1, r1[0] * d0)) + p[B];
-                    const float u2 = fmaf(r2[2], d2, fmaf(r2[1], d1, r2[0] * d0)) + p[2 * B];
+                    const float u0 = row_linear(r0[0], r0[1], r0[2], d0, d1, d2) + p[0];
+                    const float u1 = row_linear(r1[0], r1[1], r1[2], d0, d1, d2) + p[B];
+                    const float u2 = row_linear(r2[0], r2[1], r2[2], d0, d1, d2) + p[2 * B];
                     acc[3 * i] = fmaf(w, u0, acc[3 * i]);
                     acc[3 * i + 1] = fmaf(w, u1, acc[3 * i + 1]);
                     acc[3 * i + 2] = fmaf(w, u2, acc[3 * i + 2]);
@@ -133,12 +109,11 @@ __global__ __launch_bounds__(64 * fkshape::JW) void fk_shape_jacobian_kernel(FkS
 
 hipError_t launch_fk_shape_jacobian(const FkShapeArgs& a, hipStream_t st) {
     if (a.B <= 0 || a.n_sel <= 0 || a.n_sel > FKJ_MAX_SEL || a.nb <= 0 || a.nb > FKS_MAX_NB || a.ns < a.nb || !a.jac || !a.sw ||
-        !a.ajt || !a.jd || !a.parents || (a.nz != 0 && a.nz != 4 && a.nz != 8 && a.nz != 16) || (a.nz && !a.nzw))
+        !a.ajt || !a.jd || !a.parents || !nz_ok(a))
         return hipErrorInvalidValue;
     (void)hipGetLastError();
-    const unsigned tiles = (a.B + fkshape::TB - 1) / fkshape::TB;
+    const unsigned tiles = (a.B + TB - 1) / TB;
     hipLaunchKernelGGL(fk_shape_pre_kernel, dim3(tiles, a.nb), dim3(64), 0, st, a);
-    constexpr int JW = fkshape::JW;
     hipLaunchKernelGGL(fk_shape_jacobian_kernel, dim3(tiles, (a.n_sel + JW - 1) / JW), dim3(64 * JW), 0, st, a);
     return hipGetLastError();
 }

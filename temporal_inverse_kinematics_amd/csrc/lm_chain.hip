@@ -14,7 +14,8 @@
 //     replace row f; then M = L_f^-1 (thread c = column c by forward substitution, no barrier inside) and
 //     S_f^-1 = M^T M (the packed triangle spread over the 256 threads, k ascending) for the next frame;
 //   backward, frames descending: delta_{b-1} = x_{b-1}, delta_f = fmaf(smooth, (L_f L_f^T)^-1 delta_{f+1}, x_f),
-//     L_f and x_f read back from row f.
+//     L_f and x_f read back from row f, the two solves by lm_solve_factored.
+// lm_dev.h holds every piece named above that lm_solve.hip has too (accumulation, damping, factor, solves, lm_untri).
 // The off-diagonal blocks being a multiple of the identity is what keeps this small: no block is ever
 // multiplied by another. With smooth == 0, or in a sequence of one frame, no term of the coupling is
 // formed at all and delta is bit for bit lm_solve.hip's. A pivot that is not positive (or NaN) at any
@@ -22,7 +23,6 @@
 // sequence whose bounds are not 0 <= a < b <= F does no work, and a frame that no such sequence holds is
 // skipped: no index leaves [0, F) whatever seq_starts holds. A sequence's arithmetic does not see the
 // launch, so its bits are the same for any S. No atomics, no waiting between workgroups.
-#include "common.h"
 #include "dev_common.h"
 #include "lm_dev.h"
 
@@ -53,14 +53,6 @@ struct LmChainArgs {
     float* delta;           // (F,n)
 };
 
-// Row and column of entry e of a packed lower triangle.
-__device__ __forceinline__ void lm_untri(int e, int& i, int& j) {
-    i = (int)((sqrtf(8.f * (float)e + 1.f) - 1.f) * 0.5f);
-    while (lm_tri(i) > e) --i;
-    while (lm_tri(i + 1) <= e) ++i;
-    j = e - lm_tri(i);
-}
-
 __global__ __launch_bounds__(LM_T) void lm_chain_accumulate_kernel(LmChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int n = a.n, m = a.m, tid = threadIdx.x, ntri = lm_tri(n);
@@ -74,17 +66,18 @@ __global__ __launch_bounds__(LM_T) void lm_chain_accumulate_kernel(LmChainArgs a
     const int q = lo, fa = a.seq_starts[q], fb = a.seq_starts[q + 1];
     if (!(0 <= fa && fa <= f && f < fb && fb <= a.F)) return;   // the whole workgroup, before any barrier
     const LmLds s(smem, n);
-    for (int e = tid; e < ntri + n; e += LM_T) s.sN[e] = 0.f;   // sG follows sN
+    lm_clear(s, n);
     __syncthreads();
     lm_accumulate_body(s, a.jac + (size_t)f * m * n, a.r + (size_t)f * m,
                        a.row_w ? a.row_w + (size_t)f * a.row_w_stride : nullptr, m, n);
     const bool prev = f > fa, next = f + 1 < fb;
     const float c = (float)((int)prev + (int)next);
+    // the coupling's share of the diagonal is in lm_damp's one argument; its share of the gradient joins g + mu prior
+    // below, before the negation
+    float g = lm_damp(s, n, (a.mu + a.lambda[q]) + a.smooth * c, a.mu, a.prior ? a.prior + (size_t)f * n : nullptr);
     if (tid < n) {
         const int i = tid;
         const size_t at = (size_t)f * n + i;
-        s.sN[lm_tri(i) + i] += (a.mu + a.lambda[q]) + a.smooth * c;
-        float g = a.prior ? fmaf(a.mu, a.prior[at], s.sG[i]) : s.sG[i];
         if (a.smooth != 0.f && c != 0.f) {
             float t = c * a.theta[at];
             if (prev) t -= a.theta[at - n];
@@ -96,27 +89,6 @@ __global__ __launch_bounds__(LM_T) void lm_chain_accumulate_kernel(LmChainArgs a
     __syncthreads();
     float* o = a.ws + (size_t)f * (ntri + n);
     for (int e = tid; e < ntri + n; e += LM_T) o[e] = s.sN[e];
-}
-
-// L y = x and L^T z = y with L in sN (lm_factor_solve's two solves, on a factor that is already there);
-// thread i = row i, x its right-hand side -> z in sG. Called by the whole workgroup after a barrier
-// behind the last write of sN.
-__device__ __forceinline__ void lm_solve_factored(const LmLds& s, int n, float x) {
-    float *sN = s.sN, *sG = s.sG, *sY = s.sY;
-    const int i = threadIdx.x;
-    const bool own = i < n;
-    const int ti = lm_tri(own ? i : 0);
-    for (int j = 0; j < n; ++j) {
-        if (i == j) sY[j] = x / sN[ti + j];
-        __syncthreads();
-        if (own && i > j) x = fmaf(-sN[ti + j], sY[j], x);
-    }
-    if (own) x = sY[i];
-    for (int j = n - 1; j >= 0; --j) {
-        if (i == j) sG[j] = x / sN[ti + j];
-        __syncthreads();
-        if (own && i < j) x = fmaf(-sN[lm_tri(j) + i], sG[j], x);
-    }
 }
 
 __global__ __launch_bounds__(LM_T) void lm_chain_sweep_kernel(LmChainArgs a) {
@@ -165,8 +137,7 @@ __global__ __launch_bounds__(LM_T) void lm_chain_sweep_kernel(LmChainArgs a) {
             __syncthreads();
             // S_f^-1 = M^T M: entry (p, j <= p) = sum_{k >= p} M[k][p] M[k][j], k ascending
             for (int e = tid; e < ntri; e += LM_T) {
-                int p, j;
-                lm_untri(e, p, j);
+                const int p = lm_untri(e), j = e - lm_tri(p);
                 float acc = 0.f;
                 for (int k = p; k < n; ++k) acc = fmaf(sM[lm_tri(k) + p], sM[lm_tri(k) + j], acc);
                 sInv[e] = acc;
@@ -214,21 +185,12 @@ extern "C" int tik_lm_solve_chain(const float* jac, const float* r, const float*
         return fail(TIK_E_INVALID, "tik_lm_solve_chain: null pointer");
     if (F <= 0) return fail(TIK_E_INVALID, "tik_lm_solve_chain: F must be positive, got %d", F);
     if (S < 1 || S > F) return fail(TIK_E_INVALID, "tik_lm_solve_chain: S must be 1..F = %d, got %d", F, S);
-    if (n < 1 || n > tik::LM_CHAIN_MAX_N)
-        return fail(TIK_E_INVALID, "tik_lm_solve_chain: n must be 1..%d, got %d", tik::LM_CHAIN_MAX_N, n);
-    if (m < 1 || m > tik::LM_MAX_M) return fail(TIK_E_INVALID, "tik_lm_solve_chain: m must be 1..%d, got %d", tik::LM_MAX_M, m);
-    if (!(mu >= 0.f)) return fail(TIK_E_INVALID, "tik_lm_solve_chain: mu must be >= 0, got %g", (double)mu);
+    if (int rc = tik::lm_check_range("tik_lm_solve_chain", n, tik::LM_CHAIN_MAX_N, &m, &mu)) return rc;
     if (!(smooth >= 0.f)) return fail(TIK_E_INVALID, "tik_lm_solve_chain: smooth must be >= 0, got %g", (double)smooth);
     if (!theta && smooth != 0.f) return fail(TIK_E_INVALID, "tik_lm_solve_chain: theta may be null only with smooth == 0");
     if (row_w_stride != 0 && row_w_stride != m)
         return fail(TIK_E_INVALID, "tik_lm_solve_chain: row_w_stride must be 0 or m = %d, got %d", m, row_w_stride);
-    tik::LmChainArgs a{F, S, m, n, row_w_stride, mu, smooth, jac, r, prior, theta, row_w, lambda, seq_starts, workspace, delta};
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(tik::lm_chain_accumulate_kernel, dim3(F), dim3(tik::LM_T), tik::lm_lds_floats(n) * sizeof(float),
-                       (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tik::lm_chain_sweep_kernel, dim3(S), dim3(tik::LM_T), tik::lm_chain_lds_floats(n) * sizeof(float),
-                       (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return TIK_OK;
+    const tik::LmChainArgs a{F, S, m, n, row_w_stride, mu, smooth, jac, r, prior, theta, row_w, lambda, seq_starts, workspace, delta};
+    if (int rc = tik::lm_launch(tik::lm_chain_accumulate_kernel, F, tik::lm_lds_floats(n), stream, a)) return rc;
+    return tik::lm_launch(tik::lm_chain_sweep_kernel, S, tik::lm_chain_lds_floats(n), stream, a);
 }

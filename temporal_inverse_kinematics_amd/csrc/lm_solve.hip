@@ -13,12 +13,11 @@
 // A pivot that is not positive (or NaN) sets a flag, the factorisation stops at that column for
 // the whole workgroup, and the body's delta is NaN; nothing loops on it. Only delta goes back
 // to HBM. A body's arithmetic does not see the batch, so its bits are the same for any B.
-#include "common.h"
 #include "dev_common.h"
 #include "lm_dev.h"
 
-// The accumulation (1.) and the factorisation with its solves (3., 4.) live in lm_dev.h, shared with
-// lm_sum.hip.
+// Every numbered step lives in lm_dev.h, shared with lm_sum.hip and lm_chain.hip; so do the entry point's
+// range checks and its launch.
 namespace tik {
 
 struct LmArgs {
@@ -34,27 +33,20 @@ struct LmArgs {
 
 __global__ __launch_bounds__(LM_T) void lm_solve_kernel(LmArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int n = a.n, m = a.m, tid = threadIdx.x, ntri = lm_tri(n);
+    const int n = a.n, m = a.m;
     const size_t b = blockIdx.x;
     const LmLds s(smem, n);
-    for (int e = tid; e < ntri; e += LM_T) s.sN[e] = 0.f;
-    for (int i = tid; i < n; i += LM_T) s.sG[i] = 0.f;
-    if (tid == 0) s.sP[1] = 0.f;
+    lm_clear(s, n);
     __syncthreads();
     // 1. normal matrix and gradient, rows ascending
     lm_accumulate_body(s, a.jac + b * m * n, a.r + b * m, a.row_w, m, n);
     // 2. damping and right-hand side; from here thread i owns row i (n <= 165 < LM_T)
-    const int i = tid;
-    const bool own = i < n;
-    float x = 0.f;
-    if (own) {
-        s.sN[lm_tri(i) + i] += a.mu + a.lambda[b];
-        x = -(a.prior ? fmaf(a.mu, a.prior[b * n + i], s.sG[i]) : s.sG[i]);
-    }
+    const int i = threadIdx.x;
+    const float x = -lm_damp(s, n, a.mu + a.lambda[b], a.mu, a.prior ? a.prior + b * n : nullptr);
     __syncthreads();
     // 3. Cholesky, 4. L y = rhs, then L^T delta = y
     const bool ok = lm_factor_solve(s, n, x);
-    if (own) a.delta[b * n + i] = ok ? s.sG[i] : __builtin_nanf("");
+    if (i < n) a.delta[b * n + i] = ok ? s.sG[i] : __builtin_nanf("");
 }
 
 }  // namespace tik
@@ -65,13 +57,7 @@ extern "C" int tik_lm_solve(const float* jac, const float* r, const float* prior
                             float mu, int B, int m, int n, float* delta, void* stream) {
     if (!jac || !r || !lambda || !delta) return fail(TIK_E_INVALID, "tik_lm_solve: null pointer");
     if (B <= 0) return fail(TIK_E_INVALID, "tik_lm_solve: B must be positive, got %d", B);
-    if (n < 1 || n > tik::LM_MAX_N) return fail(TIK_E_INVALID, "tik_lm_solve: n must be 1..%d, got %d", tik::LM_MAX_N, n);
-    if (m < 1 || m > tik::LM_MAX_M) return fail(TIK_E_INVALID, "tik_lm_solve: m must be 1..%d, got %d", tik::LM_MAX_M, m);
-    if (!(mu >= 0.f)) return fail(TIK_E_INVALID, "tik_lm_solve: mu must be >= 0, got %g", (double)mu);
-    tik::LmArgs a{B, m, n, mu, jac, r, prior, row_w, lambda, delta};
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(tik::lm_solve_kernel, dim3(B), dim3(tik::LM_T), tik::lm_lds_floats(n) * sizeof(float),
-                       (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return TIK_OK;
+    if (int rc = tik::lm_check_range("tik_lm_solve", n, tik::LM_MAX_N, &m, &mu)) return rc;
+    const tik::LmArgs a{B, m, n, mu, jac, r, prior, row_w, lambda, delta};
+    return tik::lm_launch(tik::lm_solve_kernel, B, tik::lm_lds_floats(n), stream, a);
 }

@@ -9,9 +9,8 @@
 // on its own bodies only. Row q of partial: the triangle (n (n + 1) / 2 floats), then the gradient (n).
 // lm_solve_sum_kernel: one workgroup adds the n_part rows in ascending order, puts mu + lambda on
 // the diagonal, forms -(g + mu prior), then factors and solves exactly as lm_solve.hip does
-// (lm_dev.h). A pivot that is not positive writes NaN into delta and nothing else.
+// (lm_dev.h: lm_damp, lm_factor_solve). A pivot that is not positive writes NaN into delta and nothing else.
 // No atomics, no waiting between workgroups, plain vector stores.
-#include "common.h"
 #include "dev_common.h"
 #include "lm_dev.h"
 
@@ -37,7 +36,7 @@ __global__ __launch_bounds__(LM_T) void lm_accumulate_kernel(LmAccArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int n = a.n, m = a.m, tid = threadIdx.x, ntri = lm_tri(n);
     const LmLds s(smem, n);
-    for (int e = tid; e < ntri + n; e += LM_T) s.sN[e] = 0.f;   // sG follows sN
+    lm_clear(s, n);
     __syncthreads();
     const int b0 = blockIdx.x * LM_RUN, b1 = min(a.B, b0 + LM_RUN);
     for (int b = b0; b < b1; ++b) lm_accumulate_body(s, a.jac + (size_t)b * m * n, a.r + (size_t)b * m, a.row_w, m, n);
@@ -56,16 +55,11 @@ __global__ __launch_bounds__(LM_T) void lm_solve_sum_kernel(LmSumArgs a) {
     }
     if (tid == 0) s.sP[1] = 0.f;
     __syncthreads();
-    const int i = tid;
-    const bool own = i < n;
-    float x = 0.f;
-    if (own) {
-        s.sN[lm_tri(i) + i] += a.mu + a.lambda;
-        x = -(a.prior ? fmaf(a.mu, a.prior[i], s.sG[i]) : s.sG[i]);
-    }
+    const float x = -lm_damp(s, n, a.mu + a.lambda, a.mu, a.prior);
     __syncthreads();
     const bool ok = lm_factor_solve(s, n, x);
-    if (own) a.delta[i] = ok ? s.sG[i] : __builtin_nanf("");
+    const int i = tid;
+    if (i < n) a.delta[i] = ok ? s.sG[i] : __builtin_nanf("");
 }
 
 }  // namespace tik
@@ -76,28 +70,18 @@ extern "C" int tik_lm_accumulate(const float* jac, const float* r, const float* 
                                  float* partial, void* stream) {
     if (!jac || !r || !partial) return fail(TIK_E_INVALID, "tik_lm_accumulate: null pointer");
     if (B <= 0) return fail(TIK_E_INVALID, "tik_lm_accumulate: B must be positive, got %d", B);
-    if (n < 1 || n > tik::LM_MAX_N) return fail(TIK_E_INVALID, "tik_lm_accumulate: n must be 1..%d, got %d", tik::LM_MAX_N, n);
-    if (m < 1 || m > tik::LM_MAX_M) return fail(TIK_E_INVALID, "tik_lm_accumulate: m must be 1..%d, got %d", tik::LM_MAX_M, m);
+    if (int rc = tik::lm_check_range("tik_lm_accumulate", n, tik::LM_MAX_N, &m, nullptr)) return rc;
     static_assert(tik::LM_RUN == TIK_LM_RUN, "include/tik.h states the run length");
-    tik::LmAccArgs a{B, m, n, jac, r, row_w, partial};
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(tik::lm_accumulate_kernel, dim3((B + tik::LM_RUN - 1) / tik::LM_RUN), dim3(tik::LM_T),
-                       tik::lm_lds_floats(n) * sizeof(float), (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return TIK_OK;
+    const tik::LmAccArgs a{B, m, n, jac, r, row_w, partial};
+    return tik::lm_launch(tik::lm_accumulate_kernel, (B + tik::LM_RUN - 1) / tik::LM_RUN, tik::lm_lds_floats(n), stream, a);
 }
 
 extern "C" int tik_lm_solve_sum(const float* partial, int n_part, const float* prior, float mu, float lambda, int n,
                                 float* delta, void* stream) {
     if (!partial || !delta) return fail(TIK_E_INVALID, "tik_lm_solve_sum: null pointer");
     if (n_part <= 0) return fail(TIK_E_INVALID, "tik_lm_solve_sum: n_part must be positive, got %d", n_part);
-    if (n < 1 || n > tik::LM_MAX_N) return fail(TIK_E_INVALID, "tik_lm_solve_sum: n must be 1..%d, got %d", tik::LM_MAX_N, n);
-    if (!(mu >= 0.f)) return fail(TIK_E_INVALID, "tik_lm_solve_sum: mu must be >= 0, got %g", (double)mu);
+    if (int rc = tik::lm_check_range("tik_lm_solve_sum", n, tik::LM_MAX_N, nullptr, &mu)) return rc;
     if (!(lambda >= 0.f)) return fail(TIK_E_INVALID, "tik_lm_solve_sum: lambda must be >= 0, got %g", (double)lambda);
-    tik::LmSumArgs a{n_part, n, mu, lambda, partial, prior, delta};
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(tik::lm_solve_sum_kernel, dim3(1), dim3(tik::LM_T), tik::lm_lds_floats(n) * sizeof(float),
-                       (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return TIK_OK;
+    const tik::LmSumArgs a{n_part, n, mu, lambda, partial, prior, delta};
+    return tik::lm_launch(tik::lm_solve_sum_kernel, 1, tik::lm_lds_floats(n), stream, a);
 }

@@ -97,6 +97,28 @@ def test_dense_weight_rows_vs_oracle():
     assert err < S.TOL
 
 
+@pytest.mark.parametrize("nzmax", [4, 12, 20])
+def test_weight_layouts(nzmax):
+    """The weights of tests/test_gpu_fk_joints.py::test_weight_layouts on the small constants: 4 and 16 pairs per
+    vertex and more than 16 live joints (no pairs: the dense WT rows). One full tile plus one body, 19 columns (a
+    partial last workgroup of the 4-wave kernel); bodies 0, 63, 64 against the oracle on the same weights."""
+    import fkref
+    me.lib()
+    c = dict(R.small_consts())
+    c["lbs_weights"] = fkref._nz_weights(c["v_template"].shape[0], nzmax)
+    lo, hi = {4: (1, 4), 12: (9, 16), 20: (17, 55)}[nzmax]   # live joints of the fullest vertex: 4 pairs, 16 pairs, none
+    assert lo <= int(fkref.live_counts(c).max()) <= hi
+    with me.env(TIK_FK_SKIN="sparse"):
+        m = S.SMPLX(c, batch_size=9)
+    jac, _ = m.joints_shape_jacobian(*args65(False, 65), select=SEL)
+    assert torch.isfinite(jac).all()
+    bodies = [0, 63, 64]
+    ref = S.oracle_shape_jacobian(c, R.inputs65()[0], SEL, bodies=bodies)
+    err = np.abs(jac[bodies].cpu().numpy() - ref).max()
+    print(f"nzmax={nzmax}: max |jac - oracle| = {err:.3e}")
+    assert err < S.TOL
+
+
 # ---------------------------------------------------------------- 2. each term is visible
 def test_each_term_is_visible(model):
     c = R.small_consts()
