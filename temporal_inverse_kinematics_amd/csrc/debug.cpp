@@ -72,23 +72,23 @@ static hipError_t launch_traced(size_t slots, hipStream_t st, Launch launch, Rep
     return e;
 }
 
-// xgemm.hip: 8 stamps per workgroup (s_memtime cycles)
+// xgemm.hip: 8 slots per workgroup (s_memtime cycles)
 hipError_t launch_xgemm_traced(tik::XArgs a, int bn, int epi, hipStream_t st, const char* label) {
-    const int rt = tik::xgemm_tile_rows(epi, a.nw);
+    const int rt = tik::xgemm_tile_rows(epi);
     const long long nwg = (long long)((a.M + rt - 1) / rt) * ((a.Nc + bn - 1) / bn);
     return launch_traced(nwg * 8, st,
         [&](unsigned long long* d) { a.trace = d; return tik::launch_xgemm(a, bn, epi, st); },
         [&](const std::vector<unsigned long long>& h) {
-            double s[6] = {0, 0, 0, 0, 0, 0}, n = 0, ks = 0;
+            double s[5] = {0, 0, 0, 0, 0}, n = 0, ks = 0;
             for (long long w = 0; w < nwg; ++w) {
-                if (!h[8 * w + 7]) continue;
-                n += 1; ks = (double)h[8 * w + 6];
-                for (int k = 0; k < 6; ++k) s[k] += (double)h[8 * w + k];
+                if (!h[8 * w + 6]) continue;
+                n += 1; ks = (double)h[8 * w + 5];
+                for (int k = 0; k < 5; ++k) s[k] += (double)h[8 * w + k];
             }
             n = std::max(1.0, n);
-            fprintf(stderr, "XTRACE %-10s wg %6.0f ksteps %3.0f | cycles/wg: prologue %7.0f main %8.0f iden %6.0f epi %7.0f | "
-                    "barrier %7.0f vmwait %7.0f | main/kstep %6.0f\n", label, n, ks, s[0] / n, s[1] / n, s[2] / n, s[3] / n,
-                    s[4] / n, s[5] / n, s[1] / n / std::max(1.0, ks));
+            fprintf(stderr, "XTRACE %-10s wg %6.0f ksteps %3.0f | cycles/wg: prologue %7.0f main %8.0f epi %7.0f | "
+                    "barrier %7.0f vmwait %7.0f | main/kstep %6.0f\n", label, n, ks, s[0] / n, s[1] / n, s[2] / n,
+                    s[3] / n, s[4] / n, s[1] / n / std::max(1.0, ks));
         });
 }
 

@@ -111,4 +111,12 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_s_barrier();
 }
 
+// XCD-aware order of n work items: consecutive workgroup ids go to different
+// XCDs (id & 7), so id -> a slot such that each XCD owns a contiguous run of
+// slots (rows or weights shared by neighbouring slots stay in its L2)
+__device__ __forceinline__ int xcd_slot(int id, int n) {
+    const int per = n >> 3, rem = n & 7, x = id & 7, k = id >> 3;
+    return x < rem ? x * (per + 1) + k : rem * (per + 1) + (x - rem) * per + k;
+}
+
 }  // namespace tik

@@ -170,8 +170,8 @@ int tik_fk_forward(tik_fk_t fk, const float* full_pose, const float* betas, cons
         tik::XArgs g{};
         g.M = n; g.Nc = V3; g.V = 1; g.tout = n;
         g.seg[0] = tik::XSeg{fk->feat.p + (size_t)b0 * KP, KP, KP, 1, 1, 0, n, n};
-        g.nseg = 1; g.wp = fk->xPT.p; g.ksteps = tik::xgemm_ksteps(g);
-        g.out = vp; g.ldo = fk->ldv; g.act = tik::ACT_NONE; g.epi_lds = 1;
+        g.nseg = 1; g.wp = fk->xPT.p;
+        g.out = vp; g.ldo = fk->ldv; g.act = tik::ACT_NONE;
         // P^T (V3 x 512 bf16x3, ~97 MB) is the large operand: group the row tiles so each XCD
         // streams it about once (its contiguous run of workgroups covers gm row tiles x all columns)
         { const int gx = (n + 127) / 128; g.gm = (gx + 7) / 8; }
@@ -237,7 +237,7 @@ int tik_fk_forward(tik_fk_t fk, const float* full_pose, const float* betas, cons
         tik::XArgs s{};
         s.M = B * ar; s.Nc = fk->V; s.V = 1; s.tout = B * ar;
         s.seg[0] = tik::XSeg{fk->ablk.p, KJ, KJ, 1, 1, 0, B * ar, (long long)B * ar};
-        s.nseg = 1; s.wp = fk->xWT.p; s.ksteps = tik::xgemm_ksteps(s); s.skin_rows = ar;
+        s.nseg = 1; s.wp = fk->xWT.p; s.skin_rows = ar;
         s.resid = fk->vposed.p; s.ldr = fk->ldv; s.out = vout; s.ldo = V3; s.act = tik::ACT_NONE;
         s.bias = tr;
         s.trash = reinterpret_cast<float*>(fk->trash.p);

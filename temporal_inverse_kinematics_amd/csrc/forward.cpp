@@ -91,9 +91,9 @@ int Layer::spatial_x(const float* x, int ld, int N, int tin, float* z, hipStream
         tik::XArgs g{};
         g.M = (int)rin; g.Nc = cout; g.V = V; g.tout = tin;
         g.seg[0] = tik::XSeg{x, ld, cin, 1, 1, 0, tin, rin};
-        g.nseg = 1; g.wp = xg.p; g.ksteps = xg_ks;
+        g.nseg = 1; g.wp = xg.p;
         g.bias = bias2.p; g.amix = amix.p; g.mix_sparse = mix_sparse ? 1 : 0; g.out = z; g.ldo = cout; g.act = tik::ACT_RELU;
-        g.nw = 4; g.nts = 1;
+        g.nts = 1;
         const std::string lab = std::string(xg_bn == 128 ? "XG128.L" : "XG64.L") + std::to_string(index);
         ProfScope p(lab.c_str(), gcn_work((double)rin, cin, cout, V), st);
         p.out(z, (size_t)rin * cout * 4);
@@ -137,10 +137,10 @@ int Layer::temporal_x(const float* x, int ld, int N, int tin, const float* z, fl
     } else if (res == RES_IDEN) {
         t.idn = tik::XSeg{x, ld, cin, 1, 1, 0, to, rin};
     }
-    t.wp = xt.p; t.ksteps = tik::xgemm_ksteps(t);
+    t.wp = xt.p;
     if (tik::xgemm_kmain(t) != xt_ks) return fail(TIK_E_INVALID, "layer %d: xgemm K steps %d != packed %d", index, tik::xgemm_kmain(t), xt_ks);
     t.bias = biasT.p; t.out = out; t.ldo = cout; t.act = tik::ACT_RELU;
-    t.nw = 4; t.epi_lds = 1; t.idn_epi = 1; t.nts = 1;
+    t.nts = 1;
     t.trash = xtrash;
     const bool pt = xpt_path();
     const std::string lab = std::string(xt_bn == 128 ? (pt ? "XP128.L" : "XT128.L") : (pt ? "XP64.L" : "XT64.L")) +
@@ -285,11 +285,10 @@ static int head_x(tik_model* m, const float* f, int rows, float* poses, const Wo
     tik::XArgs h{};
     h.M = rows; h.Nc = m->hidden; h.V = 1; h.tout = rows;
     h.seg[0] = tik::XSeg{f, m->feat, m->feat, 1, 1, 0, rows, rows};
-    h.nseg = 1; h.wp = m->xh0.p; h.ksteps = tik::xgemm_ksteps(h);
-    h.nw = 4; h.epi_lds = 1;
+    h.nseg = 1; h.wp = m->xh0.p;
     {   // K slices: the fixed count (4: 512 workgroups at 4096 rows), each non-empty
-        const int kper = (h.ksteps + m->XHEAD_KS - 1) / m->XHEAD_KS;
-        h.ksplit = (h.ksteps + kper - 1) / kper;
+        const int ks = tik::xgemm_kmain(h), kper = (ks + m->XHEAD_KS - 1) / m->XHEAD_KS;
+        h.ksplit = (ks + kper - 1) / kper;
     }
     if (h.ksplit > 1) {
         h.out = w.part.p; h.act = tik::ACT_NONE;

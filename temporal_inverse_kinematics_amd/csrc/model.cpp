@@ -30,7 +30,7 @@ int Layer::pack(const FoldedBlock& f) {
     if (cin % 32 == 0) {
         const tik::XPackSeg g{f.wg.data(), cinp, 1, cin};
         if ((rc = xg.upload(tik::xgemm_pack(&g, 1, cout, bn)))) return rc;
-        xg_bn = bn; xg_ks = cin / 32;
+        xg_bn = bn;
     }
     if (cout % 32 == 0) {
         tik::XPackSeg t[2] = {{f.wt.data(), TK * cout, TK, cout}, {f.wr.data(), cinp, 1, cin}};

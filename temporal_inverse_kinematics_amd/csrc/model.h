@@ -89,7 +89,7 @@ struct Layer {
     SplitW3 s3g, s3t, s3r;
     DevBuf wr0;             // layer0.hip / xblock.hip: [cout][cin] residual conv of a raw-input first layer
     DevHBuf xg, xt;         // xgemm.hip: bf16x3 tiles of the gcn (cin % 32 == 0) and of tcn (+ residual conv)
-    int xg_bn = 0, xt_bn = 0, xg_ks = 0, xt_ks = 0;
+    int xg_bn = 0, xt_bn = 0, xt_ks = 0;
     DevHBuf xtw;            // xtws.hip: weight-stationary temporal conv (128 -> 128, stride 1, identity residual)
     DevHBuf xgw;            // xgraph.hip: weight-stationary gcn (128 / 256 output channels), planes in the MFMA register layout
     DevHBuf xbg, xbt;       // xblock.hip: whole block (64 channels, stride 1), gcn / tcn planes in the MFMA register layout

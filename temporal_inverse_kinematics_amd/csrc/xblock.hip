@@ -89,9 +89,7 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
     const int ntiles = (QO + F - 1) / F;
     int t_begin, t_end;
     {   // persistent: a contiguous run of tiles per workgroup, runs ordered per XCD
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int per = nwg >> 3, rem = nwg & 7, x = bid & 7, k = bid >> 3;
-        const int s = x < rem ? x * (per + 1) + k : rem * (per + 1) + (x - rem) * per + k;
+        const int nwg = gridDim.x, s = xcd_slot(blockIdx.x, nwg);
         t_begin = (int)((long long)s * ntiles / nwg);
         t_end = (int)((long long)(s + 1) * ntiles / nwg);
     }

@@ -39,12 +39,9 @@ struct XArgs {
     XSeg seg[2];
     int nseg;
     const unsigned short* wp;   // packed weight tiles (xgemm_pack), [Nc/BN][kmain][3][BN*32] bf16
-    int ksteps;                 // K steps of all segments (xgemm_ksteps)
     // identity residual (EPI_BIAS): idn.src = the block input rows, read at the
-    // output row (kt 1, stride 1, pad 0); null = none. Added inside the K loop
-    // as idn.cin/32 extra K steps against the identity (x = p0 + p1 + p2, three
-    // MFMAs with a constant 1.0 operand: an exact add), so its rows stream
-    // through the DMA ring with the other operands instead of the epilogue
+    // output row (kt 1, stride 1, pad 0, cin = Nc); null = none. Added in the
+    // epilogue from row-major loads, before the bias: (acc + x) + bias
     XSeg idn;
     const float* bias;          // EPI_BIAS: [Nc]; EPI_GRAPH: [V][Nc]
     const float* rx;            // EPI_BIAS small residual conv input [M][4] fp32 (layer 0; or null)
@@ -64,34 +61,29 @@ struct XArgs {
     // blockIdx.z = k slice; slice z writes its raw partial sums to
     // out + z * M * ldo, and xgemm_splitk_reduce finishes (0 or 1: no split)
     int ksplit;
-    int idn_epi;  // with epi_lds: the identity residual added in the epilogue from row-major loads (no K steps)
-    int epi_lds;  // EPI_BIAS: stage the C tile through LDS for whole-line row-major stores (else float4 stores from registers)
     int gm;     // xgemm_kernel tile order: >1 = groups of gm row tiles, columns outer within a group (the B operand
                 // is shared by the gm row tiles running together: for a large B, e.g. the FK blend shapes); else rows outer
-    int nw;     // waves per workgroup: 4 (or 0: two 128-row workgroups per CU) or 8 (one 256-row workgroup)
     int tune;   // experiments only (0 = production): 1 skip the A DMA, 2 skip the B DMA, 8 skip the split
-    unsigned long long* trace;   // debug (TIK_X_TRACE): 8 s_memtime stamps/sums per workgroup, or null
+    unsigned long long* trace;   // debug (TIK_X_TRACE): 8 slots of s_memtime stamps/sums per workgroup, or null
 };
 
-// K steps with packed weight tiles (the segments), and all K steps (+ identity)
+// K steps: one packed weight tile per (segment, 32-channel block, tap)
 __host__ __device__ inline int xgemm_kmain(const XArgs& a) {
     int k = 0;
     for (int s = 0; s < a.nseg; ++s) k += a.seg[s].kt * (a.seg[s].cin / 32);
     return k;
 }
-__host__ __device__ inline int xgemm_ksteps(const XArgs& a) { return xgemm_kmain(a) + (a.idn.src ? a.idn.cin / 32 : 0); }
 
-// epi: EPI_BIAS (cgemm.h: bias + residual + activation), EPI_GRAPH (graph
-// mix over the 17 joints + bias2[w][c] + ReLU) or EPI_SKIN (SMPL-X skinning:
-// rows = body * 16 + transform entry, columns = vertices); bn: 64 or 128 output columns per tile
+// epi: EPI_BIAS (cgemm.h: bias + residual + activation) or EPI_GRAPH (graph
+// mix over the 17 joints + bias2[w][c] + ReLU); bn: 64 or 128 output columns per tile
 hipError_t launch_xgemm(const XArgs& a, int bn, int epi, hipStream_t st);
 // the persistent EPI_BIAS variant (xgemm_pt_kernel): <= 2 workgroups per CU
 // (ncu = compute units) walk the tiles with one DMA pipeline across tiles.
-// Needs Nc % bn == 0, >= 2 K steps, a.trash; identity residual read in the
-// epilogue (no identity K steps); bit-identical to launch_xgemm with epi_lds.
-// epi: EPI_BIAS or EPI_SKIN (bn 128, bias = translations (B,3), zeros if none).
+// Needs Nc % bn == 0, >= 2 K steps, a.trash; bit-identical to launch_xgemm.
+// epi: EPI_BIAS or EPI_SKIN (SMPL-X skinning: rows = body * skin_rows +
+// transform entry, columns = vertices; bn 128, bias = translations (B,3), zeros if none).
 hipError_t launch_xgemm_pt(const XArgs& a, int bn, int ncu, hipStream_t st, int epi = EPI_BIAS);
-int xgemm_tile_rows(int epi, int nw);   // output rows per workgroup (whole frames for EPI_GRAPH)
+int xgemm_tile_rows(int epi);   // output rows per workgroup (whole frames for EPI_GRAPH)
 // out[r][c] = act(sum_z part[z][r][c] + bias[c]) for the ksplit partials of a
 // split-K launch (part: [ksplit][M][Nc], fixed summation order: deterministic)
 hipError_t launch_xgemm_splitk_reduce(const float* part, int ksplit, int M, int Nc, const float* bias, int act,

@@ -1,9 +1,9 @@
 // xgemm.hip — bf16x3 implicit GEMM on fp32 activations (see xgemm.h).
 //
-// Tile: BM = 32 NW rows x BN columns. Default NW = 4: a 128-row, 256-thread
-// workgroup of <= 80 KB LDS, TWO per CU, so one workgroup's prologue (first
-// DMA round trip) and epilogue run under the other's main loop (one 256-row
-// 8-wave workgroup per CU measured 3-9 % slower; removed). Wave w owns
+// Tile: 128 rows x BN columns on 4 waves: a 256-thread workgroup of <= 80 KB
+// LDS, TWO per CU, so one workgroup's prologue (first DMA round trip) and
+// epilogue run under the other's main loop (one 256-row 8-wave workgroup per
+// CU measured 3-9 % slower). Wave w owns
 // rows 32w..32w+31 (two 16-row fragments) and ALL BN columns, so each A
 // element is read from LDS and split into bf16 planes exactly once per K
 // step, in registers, by the wave that uses it (no split pass, no extra LDS);
@@ -12,8 +12,8 @@
 // LDS, per stage: the A image (BM rows x 32 fp32 = 128 B per row) and the B
 // image (3 planes x BN columns x 32 bf16 = 64 B per column), both written by
 // LDS-DMA (buffer_load ... lds, 16 B per lane). A: 2 slots, each wave DMAs
-// its own rows 2 steps ahead (no barrier); B: LB + 1 slots, LB steps ahead,
-// one barrier per K step.
+// its own rows 2 steps ahead (no barrier); B: 2 slots, 1 step ahead, one
+// barrier per K step.
 //  * A row r, logical floats [8g+4h, 8g+4h+4) (g = k group of the MFMA
 //    operand, h = half) at 16-B unit (g + 4h) ^ ((r >> 1) & 7): the two
 //    ds_read_b128 of a fragment read are conflict-free in every lane group.
@@ -28,11 +28,11 @@
 // MFMAs, and fragment i's split for the next step runs between block i's MFMAs.
 //
 // Epilogues:
-//  * EPI_BIAS (transposed MFMA, so a lane holds 4 channels of a row): + bias
-//    (+ the layer-0 residual conv on 4-float rows) -> activation -> float4
-//    stores straight from registers; the identity residual is added before,
-//    as extra K steps of exact fp32 adds from the DMA'd block-input rows.
-//  * EPI_GRAPH: tiles of whole frames (7 or 15: 119 / 255 rows) staged through
+//  * EPI_BIAS (transposed MFMA, so a lane holds 4 channels of a row): each
+//    wave stages its 32 rows through LDS and stores them row-major in whole
+//    128-B lines: (acc + the identity residual's block-input row) + bias
+//    (+ the layer-0 residual conv on 4-float rows) -> activation.
+//  * EPI_GRAPH: tiles of whole frames (7: 119 rows) staged through
 //    LDS; z[f][w] = sum_v A[v][w] y[f][v] (the einsum of gconv_origin.py:61-63;
 //    COCO hop<=2 pattern unrolled when A_eff fits it) + bias2[w][c], ReLU
 //    (st_gcn_aaai18.py:178-179).
@@ -82,10 +82,10 @@ __device__ __forceinline__ void xmix_store(const f32x4 (&y)[17], const float (&a
 // SK: a split-K launch (XArgs::ksplit > 1; its own instantiation, so the
 // profiler tells it from the backbone's EPI_BIAS launches)
 template <int BN, int EPI, int NW_, bool SK>
-__global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs a) {
+__global__ __launch_bounds__(64 * NW_, 2) void xgemm_kernel(XArgs a) {
     using C = XCfg<BN, EPI, NW_>;
     constexpr int NW = C::NW, NT = C::NT, FM = C::FM, FN = C::FN, NIA = C::NIA, NSA = C::NSA, NSB = C::NSB,
-                  RT = C::RT, RW = C::RW, LB = C::LB, BM = C::BM;
+                  RT = C::RT, RW = C::RW, BM = C::BM;
     constexpr bool TR = C::TR;
     __shared__ __attribute__((aligned(16))) unsigned char smem[C::SMEM];   // the only LDS object
 
@@ -103,13 +103,10 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
 #else
     constexpr int tune = 0;   // experiment bits (XArgs::tune) only in a -DTIK_XTUNE build
 #endif
-    unsigned long long t0 = tr ? __builtin_amdgcn_s_memtime() : 0, t_bar = 0, t_vm = 0, t1 = 0, t2 = 0, t3 = 0;
+    unsigned long long t0 = tr ? __builtin_amdgcn_s_memtime() : 0, t_bar = 0, t_vm = 0, t1 = 0, t2 = 0;
     int r0, ntile;
-    {   // XCD-aware tile order: consecutive workgroup ids go to different XCDs,
-        // so give each XCD a contiguous run of tiles (rows shared by neighbours stay in its L2)
-        const int nwg = gridDim.x * gridDim.y, bid = blockIdx.y * gridDim.x + blockIdx.x;
-        const int per = nwg >> 3, rem = nwg & 7, x = bid & 7, k = bid >> 3;
-        const int swz = x < rem ? x * (per + 1) + k : rem * (per + 1) + (x - rem) * per + k;
+    {   // XCD-aware tile order: each XCD gets a contiguous run of tiles
+        const int swz = xcd_slot(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
         if (a.gm > 1) {   // groups of gm row tiles; within a group the gm rows of one column tile are adjacent
             const int gy = gridDim.y, g = swz / (a.gm * gy), w = swz - g * a.gm * gy;
             const int left = gridDim.x - g * a.gm, ge = left < a.gm ? left : a.gm;
@@ -141,16 +138,15 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
     for (int j = 0; j < NIA; ++j) {
         const int rr = (wave * NIA + j) * 8 + (lane >> 3);
         const int row = r0 + rr;
-        const int pl = (lane & 7) ^ xa_swz(rr);            // logical unit: g = pl & 3, h = pl >> 2
-        a_uo[j] = 32 * (pl & 3) + 16 * (pl >> 2);         // its byte offset in the 128-B K block
+        a_uo[j] = xa_dma_unit(rr, lane);
         a_ok[j] = rr < RT && row < a.M;
         const int q = a_ok[j] ? row / V : 0;
         a_w[j] = a_ok[j] ? row - q * V : 0;
         a_n[j] = q / a.tout;
         a_t[j] = q - a_n[j] * a.tout;
     }
-    // K steps with weight tiles (the identity steps follow); a split-K slice
-    // runs packed steps kb .. kb + kmain of its single kt-1 segment
+    // K steps: kmain, every one with a weight tile; a split-K slice runs packed
+    // steps kb .. kb + kmain of its single kt-1 segment
     const int kall = xgemm_kmain(a);
     int kb = 0, kmain = kall;
     if (SK) {
@@ -158,27 +154,19 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
         kb = blockIdx.z * kper;
         kmain = min(kper, kall - kb);
     }
-    // the identity residual read in the LDS epilogue (row-major whole lines) instead of as K steps
-    const bool idn_epi = TR && a.epi_lds && a.idn_epi && a.idn.src;
-    const int K = SK || idn_epi ? kmain : a.ksteps;
     // B DMA: a stage's B image is one contiguous packed block; instruction q (of NIB_TOT) copies 1 KB
     const i32x4 rB = buf_rsrc(a.wp, (unsigned)((size_t)gridDim.y * kall * C::BBYTES));
-    const int nbw = (C::NIB_TOT - wave + NW - 1) / NW;   // this wave's B instructions per stage (NIBW or NIBW - 1)
 
-    // The A cursor walks (segment, 32-channel block, tap); segment slot 0 =
-    // seg[0], 1 = seg[1] (or the identity when nseg == 1), 2 = the identity.
-    // The per-step advance reads the blocks and taps of each slot from one
-    // packed 64-bit scalar (8 bits each; a select chain over separate values
-    // becomes a scratch lookup table, a dynamically indexed XSeg a kernel-argument
-    // load, every step); the segment's geometry is re-read only when the tap changes.
-    const bool two = a.nseg > 1;
-    const unsigned long long nbkt =
-        (unsigned long long)((a.seg[0].cin >> 5) | (a.seg[0].kt << 8)) |
-        ((unsigned long long)(two ? (a.seg[1].cin >> 5) | (a.seg[1].kt << 8) : (a.idn.cin >> 5) | (a.idn.kt << 8)) << 16) |
-        ((unsigned long long)((a.idn.cin >> 5) | (a.idn.kt << 8)) << 32);
+    // The A cursor walks (segment, 32-channel block, tap). The per-step advance
+    // reads the blocks and taps of each segment from one packed scalar (8 bits
+    // each; a select chain over separate values becomes a scratch lookup table,
+    // a dynamically indexed XSeg a kernel-argument load, every step); the
+    // segment's geometry is re-read only when the segment changes.
+    const unsigned nbkt = (unsigned)((a.seg[0].cin >> 5) | (a.seg[0].kt << 8)) |
+                          ((unsigned)(a.nseg > 1 ? (a.seg[1].cin >> 5) | (a.seg[1].kt << 8) : 0) << 16);
     int ca_seg = 0, ca_tap = 0, ca_blk = kb, ca_k = 0, cb_k = 0;
     auto advance_a = [&]() __attribute__((always_inline)) {
-        const unsigned f = (unsigned)(nbkt >> (16 * ca_seg));
+        const unsigned f = nbkt >> (16 * ca_seg);
         ++ca_k;
         if (++ca_tap >= (int)((f >> 8) & 255u)) {   // taps innermost: a block's 3 taps read overlapping rows back to back
             ca_tap = 0;
@@ -193,7 +181,7 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
     auto prepare = [&]() __attribute__((always_inline)) {
         if (ca_seg == cur_seg) return;
         cur_seg = ca_seg;
-        const XSeg sg = ca_seg == 0 ? a.seg[0] : (ca_seg == 1 && two ? a.seg[1] : a.idn);
+        const XSeg sg = ca_seg == 0 ? a.seg[0] : a.seg[1];
         rA = buf_rsrc(sg.src, (unsigned)(sg.rows_in * sg.ld * 4));
         sg_tin = sg.tin;
         sg_fb = V * sg.ld * 4;
@@ -224,19 +212,13 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
         if (!(tune & 2))
 #pragma unroll
             for (int q = 0; q < C::NIBW; ++q)
-                if (q < C::NIBW - 1 || wave + q * NW < C::NIB_TOT)
-                    dma16(rB, B + (wave + q * NW) * 1024, (unsigned)((wave + q * NW) * 1024 + lane * 16), soB);
+                dma16(rB, B + (wave + q * NW) * 1024, (unsigned)((wave + q * NW) * 1024 + lane * 16), soB);
         ++cb_k;
     };
-    // vmcnt accounting: at step k this wave issues B(k + LB) (nbw instructions,
-    // NIBW or NIBW - 1) then A(k + 2) (NIA); waits count the younger ones
-    auto nA = [&](int k) __attribute__((always_inline)) { return k < K ? NIA : 0; };
-    auto nB = [&](int k) __attribute__((always_inline)) { return k < kmain ? nbw : 0; };
-    auto wait_steady = [&]() __attribute__((always_inline)) {   // NIA + this wave's full B share outstanding
-        if constexpr (C::NIB_TOT % NW == 0) wait_vm<NIA + C::NIBW>();   // every wave issues NIBW
-        else if (nbw == C::NIBW) wait_vm<NIA + C::NIBW>();
-        else wait_vm<NIA + C::NIBW - 1>();
-    };
+    // vmcnt accounting: at step k this wave issues B(k + 1) (NIBW instructions)
+    // then A(k + 2) (NIA); waits count the younger ones
+    auto nA = [&](int k) __attribute__((always_inline)) { return k < kmain ? NIA : 0; };
+    auto nB = [&](int k) __attribute__((always_inline)) { return k < kmain ? C::NIBW : 0; };
 
     f32x4 acc[FM][FN];
 #pragma unroll
@@ -246,12 +228,10 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
     const int g = lane >> 4;
     const int bsw = (-((lane & 15) >> 2)) & 3;
     const int boff = (lane & 15) * 64 + ((g ^ bsw) << 4);
-    auto mma = [&](const xbf16x8& x, const xbf16x8& w, f32x4& c) __attribute__((always_inline)) {
-        // TR: C^T = W . X^T, so lane l holds row (l & 15), channels 4(l >> 4) .. +3
-        c = TR ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0)
-               : __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, w, c, 0, 0, 0);
-    };
+    auto mma = [&](const xbf16x8& x, const xbf16x8& w, f32x4& c) __attribute__((always_inline)) { xmma<TR>(x, w, c); };
     // this wave's A fragments of a step: fp32 rows -> three bf16 planes
+    // (xgemm_pt_kernel keeps its own copy: as a shared function the reads get
+    // other registers in both kernels)
     auto read_a = [&](int k, f32x4 (&lo)[FM], f32x4 (&hi)[FM]) __attribute__((always_inline)) {
         const unsigned char* A = a_slot(k % NSA);
 #pragma unroll
@@ -265,13 +245,12 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
     f32x4 alo[FM], ahi[FM];
 
     // ---- main steps: the split of step k+1 runs under step k's MFMAs
-    // issue order: B(0) A(0) [B(1)] A(1) | per step k: B(k+LB) A(k+2), so a wait
+    // issue order: B(0) A(0) A(1) | per step k: B(k+1) A(k+2), so a wait
     // for this wave's A(k) (in issue order) also retires its B(k)
     issue_b();
     issue_a();
-    if (LB == 2 && 1 < kmain) issue_b();
-    if (1 < K) issue_a();
-    wait_vm_dyn(nA(1) + (LB == 2 ? nB(1) : 0));   // A(0) and B(0) landed
+    if (1 < kmain) issue_a();
+    wait_vm_dyn(nA(1));   // A(0) and B(0) landed
     if (tr) t1 = __builtin_amdgcn_s_memtime();
     {
         read_a(0, alo, ahi);
@@ -282,7 +261,7 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
     // reads and split into nxt interleaved between them (the loop below runs it
     // twice per iteration with the two register sets swapped: no copies)
     xbf16x8 d0[FM], d1[FM], d2[FM];
-    // ST (steady, k + 2 < kmain: B(k+LB) and A(k+2) both exist): no conditions,
+    // ST (steady, k + 2 < kmain: B(k+1) and A(k+2) both exist): no conditions,
     // compile-time waits; the last steps take the general path
     auto main_step = [&](int k, auto steady, xbf16x8 (&u0)[FM], xbf16x8 (&u1)[FM], xbf16x8 (&u2)[FM], xbf16x8 (&v0)[FM],
                          xbf16x8 (&v1)[FM], xbf16x8 (&v2)[FM]) __attribute__((always_inline)) {
@@ -291,19 +270,16 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
         const unsigned long long tb0 = tr ? __builtin_amdgcn_s_memtime() : 0;
         __builtin_amdgcn_s_barrier();   // every wave's B(k) landed; every wave done reading B(k-1)
         if (tr) t_bar += __builtin_amdgcn_s_memtime() - tb0;
-        if (ST || k + LB < kmain) issue_b();
-        if (ST || k + 2 < K) issue_a();
-        // this wave's A(k+1) landed (B(k+LB), A(k+2) may still fly); past the last
+        if (ST || k + 1 < kmain) issue_b();
+        if (ST || k + 2 < kmain) issue_a();
+        // this wave's A(k+1) landed (B(k+1), A(k+2) may still fly); past the last
         // step the read + split below run on a stale slot and are discarded
-        auto wait_a_next = [&]() __attribute__((always_inline)) {
+        {
             const unsigned long long tv0 = tr ? __builtin_amdgcn_s_memtime() : 0;
-            if (ST || k + 2 < kmain) wait_steady();
-            else wait_vm_dyn(nB(k + LB) + nA(k + 2));
+            if (ST || k + 2 < kmain) wait_vm<NIA + C::NIBW>();
+            else wait_vm_dyn(nB(k + 1) + nA(k + 2));
             if (tr) t_vm += __builtin_amdgcn_s_memtime() - tv0;
-        };
-#ifndef TIK_XORDER
-        wait_a_next();
-#endif
+        }
         const unsigned char* B = b_slot(k % NSB) + boff;
         // Software pipeline inside the step: the A reads of step k+1 and the
         // first weight block's reads, then per column block j the next block's
@@ -316,19 +292,9 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
         // blocks in this order.
         xbf16x8 bb[2][3];
         __builtin_amdgcn_sched_barrier(0);
-#ifdef TIK_XORDER
-        // B(k) is ready at the barrier: its first block's reads go out before the
-        // wait for A(k+1), so they overlap that wait and the first MFMAs need not
-        // wait for the A reads
-#pragma unroll
-        for (int p = 0; p < 3; ++p) bb[0][p] = *reinterpret_cast<const xbf16x8*>(B + p * C::PLANE);
-        wait_a_next();
-        read_a(k + 1, alo, ahi);
-#else
         read_a(k + 1, alo, ahi);
 #pragma unroll
         for (int p = 0; p < 3; ++p) bb[0][p] = *reinterpret_cast<const xbf16x8*>(B + p * C::PLANE);
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
@@ -366,7 +332,7 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (LB == 1) {   // B(k+1) landed before the next step's barrier (only A(k+2) younger)
+        {   // B(k+1) landed before the next step's barrier (only A(k+2) younger)
             const unsigned long long tv0 = tr ? __builtin_amdgcn_s_memtime() : 0;
             if (ST) wait_vm<NIA>();
             else wait_vm_dyn(nA(k + 2));
@@ -384,223 +350,82 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
         main_step(k, general, c0, c1, c2, d0, d1, d2);
         if (k + 1 < kmain) main_step(k + 1, general, d0, d1, d2, c0, c1, c2);
     }
-    if (tr) t2 = __builtin_amdgcn_s_memtime();
-    // ---- identity residual steps (TR): acc += x, exact fp32 adds from this wave's rows
-    if constexpr (TR) {
-        for (int k = kmain; k < K; ++k) {
-            wait_vm_dyn(k + 1 < K ? NIA : 0);   // A(k) landed (only A(k+1) was issued after it)
-            const unsigned char* A = a_slot(k % NSA);
-            const int blk = k - kmain;
-            const int jb = (32 * blk - n0) / 16;   // first local column block of these channels
-            f32x4 xv[FM][2];
-#pragma unroll
-            for (int i = 0; i < FM; ++i) {
-                const int r = wave * RW + i * 16 + (lane & 15);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    // channels 32 blk + 16h + 4g .. +3 = logical floats [8 g' + 4 h', +4)
-                    const int gp = 2 * h + (g >> 1), hp = g & 1;
-                    xv[i][h] = *reinterpret_cast<const f32x4*>(A + r * 128 + (((gp + 4 * hp) ^ xa_swz(r)) << 4));
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (k + 2 < K) issue_a();   // into the slot just read
-#pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                const int h = j - jb;
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-                    if (h == 0) acc[i][j] += xv[i][0];
-                    else if (h == 1) acc[i][j] += xv[i][1];
-            }
-        }
-    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tr) t3 = __builtin_amdgcn_s_memtime();
+    if (tr) t2 = __builtin_amdgcn_s_memtime();
     auto trace_out = [&]() __attribute__((always_inline)) {
         if (tr && tid == 0) {
             unsigned long long* o = a.trace + 8 * (size_t)(blockIdx.y * gridDim.x + blockIdx.x);
-            o[0] = t1 - t0; o[1] = t2 - t1; o[2] = t3 - t2; o[3] = __builtin_amdgcn_s_memtime() - t3;
-            o[4] = t_bar; o[5] = t_vm; o[6] = kmain; o[7] = 1;
+            o[0] = t1 - t0; o[1] = t2 - t1; o[2] = __builtin_amdgcn_s_memtime() - t2;
+            o[3] = t_bar; o[4] = t_vm; o[5] = kmain; o[6] = 1;
         }
     };
 
     if constexpr (TR) {
         const float slope = a.act == ACT_RELU ? 0.f : (a.act == ACT_LEAKY ? 0.01f : 1.f);
         float* const outp = SK ? a.out + (size_t)blockIdx.z * a.M * a.ldo : a.out;
-        if (a.epi_lds) {
-            // ---- EPI_BIAS through LDS: each wave stages its own 32 rows (no barrier
-            // between its writes and reads) and stores them row-major, so every
-            // store instruction writes whole 128-B lines (RPI rows x BN x 4 B)
-            // instead of 16 half lines (one 64-B piece per row)
-            constexpr int LDC = BN + 4, LPR = BN / 4, RPI = 64 / LPR, NQ = RW / RPI;
-            constexpr int NQR = BN == 64 ? NQ : 1;
-            float* Cs = reinterpret_cast<float*>(smem);
-            const int cl = 4 * (lane % LPR), col = n0 + cl, rsub = lane / LPR;
-            const bool cok = col + 3 < a.Nc;
-            // global operands before the first store (vmcnt counts loads and stores in order)
-            const f32x4 bv = a.bias && cok ? *reinterpret_cast<const f32x4*>(a.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-            float rw[4][4];
-            f32x4 xr[NQR];
+        // ---- EPI_BIAS through LDS: each wave stages its own 32 rows (no barrier
+        // between its writes and reads) and stores them row-major, so every
+        // store instruction writes whole 128-B lines (RPI rows x BN x 4 B)
+        constexpr int LDC = BN + 4, LPR = BN / 4, RPI = 64 / LPR, NQ = RW / RPI;
+        constexpr int NQR = BN == 64 ? NQ : 1;
+        float* Cs = reinterpret_cast<float*>(smem);
+        const int cl = 4 * (lane % LPR), col = n0 + cl, rsub = lane / LPR;
+        const bool cok = col + 3 < a.Nc;
+        // global operands before the first store (vmcnt counts loads and stores in order)
+        const f32x4 bv = a.bias && cok ? *reinterpret_cast<const f32x4*>(a.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+        float rw[4][4];
+        f32x4 xr[NQR];
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
+        for (int e = 0; e < 4; ++e)
 #pragma unroll
-                for (int c = 0; c < 4; ++c) rw[e][c] = BN == 64 && a.rx && c < a.rxc && col + e < a.Nc ? a.rw[(col + e) * a.rxc + c] : 0.f;
+            for (int c = 0; c < 4; ++c) rw[e][c] = BN == 64 && a.rx && c < a.rxc && col + e < a.Nc ? a.rw[(col + e) * a.rxc + c] : 0.f;
 #pragma unroll
-            for (int q = 0; q < NQR; ++q) {
-                const int lr = wave * RW + q * RPI + rsub;
-                xr[q] = BN == 64 && a.rx && lr < RT && r0 + lr < a.M ? *reinterpret_cast<const f32x4*>(a.rx + (size_t)(r0 + lr) * 4)
-                                                                      : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            constexpr int NQI = TR ? NQ : 1;
-            f32x4 xi[NQI];
-            if (idn_epi) {   // the identity residual rows (block input = output row, same channels)
-#pragma unroll
-                for (int q = 0; q < NQI; ++q) {
-                    const int lr = wave * RW + q * RPI + rsub;
-                    xi[q] = cok && lr < RT && r0 + lr < a.M
-                                ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.idn.src + (size_t)(r0 + lr) * a.idn.ld + col))
-                                : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-            }
-            __syncthreads();   // every wave done reading the ring (the B slots are shared)
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j)
-                    *reinterpret_cast<f32x4*>(Cs + (wave * RW + 16 * i + (lane & 15)) * LDC + 16 * j + 4 * g) = acc[i][j];
+        for (int q = 0; q < NQR; ++q) {
+            const int lr = wave * RW + q * RPI + rsub;
+            xr[q] = BN == 64 && a.rx && lr < RT && r0 + lr < a.M ? *reinterpret_cast<const f32x4*>(a.rx + (size_t)(r0 + lr) * 4)
+                                                                  : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        const bool idn = a.idn.src != nullptr;
+        f32x4 xi[NQ];
+        if (idn) {   // the identity residual rows (block input = output row, same channels)
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const int lr = wave * RW + q * RPI + rsub;
-                f32x4 v = *reinterpret_cast<const f32x4*>(Cs + lr * LDC + cl);
-                if (idn_epi) v += xi[q % NQI];   // same order as the K-step adds: (acc + x) + bias
-                v += bv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (BN == 64 && a.rx) v[e] += xr[q % NQR][0] * rw[e][0] + xr[q % NQR][1] * rw[e][1] + xr[q % NQR][2] * rw[e][2] + xr[q % NQR][3] * rw[e][3];
-                    v[e] = v[e] > 0.f ? v[e] : slope * v[e];
-                }
-                if (lr < RT && r0 + lr < a.M) {
-                    if (cok) {
-                        xst4(outp + (size_t)(r0 + lr) * a.ldo + col, v, a.nts);
-                    } else {
-                        for (int e = 0; e < 4 && col + e < a.Nc; ++e) {
-                            float t = *(Cs + lr * LDC + cl + e) + (a.bias ? a.bias[col + e] : 0.f);
-                            if (a.rx)
-                                for (int c = 0; c < a.rxc; ++c) t = fmaf(xr[q % NQR][c], a.rw[(col + e) * a.rxc + c], t);
-                            outp[(size_t)(r0 + lr) * a.ldo + col + e] = t > 0.f ? t : slope * t;
-                        }
-                    }
-                }
-            }
-            trace_out();
-            return;
-        }
-        // ---- EPI_BIAS from registers: acc[i][j] lane l = row wave*32 + 16i + (l & 15),
-        // channels n0 + 16j + 4(l >> 4) .. +3: float4 operands and stores, no LDS
-        int rows[FM];
-        bool rok[FM];
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-            const int lr = wave * RW + i * 16 + (lane & 15);
-            rok[i] = lr < RT && r0 + lr < a.M;
-            rows[i] = rok[i] ? r0 + lr : 0;
-        }
-        f32x4 xr[FM];
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-            xr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (a.rx) xr[i] = *reinterpret_cast<const f32x4*>(a.rx + (size_t)rows[i] * 4);
-        }
-        // every global operand is loaded before the first store: a load issued
-        // after a store waits for that store too (vmcnt counts both, in order)
-        f32x4 bvs[FN];
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-            const int col = n0 + 16 * j + 4 * g;
-            bvs[j] = a.bias && col + 3 < a.Nc ? *reinterpret_cast<const f32x4*>(a.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        // layer 0's residual conv weights (BN 64 tiles only, launch_xgemm checks)
-        constexpr int FNR = BN == 64 ? FN : 1;
-        float rws[FNR][4][4];
-#pragma unroll
-        for (int j = 0; j < FNR; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int col = n0 + 16 * j + 4 * g + e;
-                    rws[j][e][c] = BN == 64 && a.rx && c < a.rxc && col < a.Nc ? a.rw[col * a.rxc + c] : 0.f;
-                }
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-            const int col = n0 + 16 * j + 4 * g;
-            if (col >= a.Nc) continue;
-            if (col + 3 < a.Nc) {
-                const f32x4 bv = bvs[j];
-                float rw[4][4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) rw[e][c] = rws[j % FNR][e][c];
-#pragma unroll
-                for (int i = 0; i < FM; ++i) {
-                    f32x4 v = acc[i][j] + bv;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v[e] += xr[i][0] * rw[e][0] + xr[i][1] * rw[e][1] + xr[i][2] * rw[e][2] + xr[i][3] * rw[e][3];
-                        v[e] = v[e] > 0.f ? v[e] : slope * v[e];
-                    }
-                    if (rok[i]) xst4(outp + (size_t)rows[i] * a.ldo + col, v, a.nts);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < FM; ++i) {
-                    if (!rok[i]) continue;
-                    for (int e = 0; e < 4 && col + e < a.Nc; ++e) {
-                        float t = acc[i][j][e] + (a.bias ? a.bias[col + e] : 0.f);
-                        if (a.rx)
-                            for (int c = 0; c < a.rxc; ++c) t = fmaf(xr[i][c], a.rw[(col + e) * a.rxc + c], t);
-                        t = t > 0.f ? t : slope * t;
-                        outp[(size_t)rows[i] * a.ldo + col + e] = t;
-                    }
-                }
+                xi[q] = cok && lr < RT && r0 + lr < a.M
+                            ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.idn.src + (size_t)(r0 + lr) * a.idn.ld + col))
+                            : f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
-    } else if constexpr (EPI == EPI_SKIN) {
-        // ---- SMPL-X skinning (lbs): rows = body * 16 + transform entry e of
-        // T_v(b) = sum_j W[v][j] A_j(b); a 16-row fragment is one body and lane
-        // group g holds entries 4g..4g+3 = transform row g of vertex n0 + 16j +
-        // (lane & 15). verts[b][3v + g] = T[g][:3] . v_posed[b][3v..] + T[g][3]
-        // (+ transl[b][g]), the fma chain of cgemm.hip's EPI_SKIN.
-        // Every global operand is loaded before the first store.
-        const int vl = lane & 15;
-        float vpr[FM][FN][3], tb[FM];
-        int bdy[FM];
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-            bdy[i] = (r0 + wave * RW + 16 * i) >> 4;
-            const bool bok = g < 3 && bdy[i] * 16 < a.M;
-            tb[i] = bok && a.bias ? a.bias[bdy[i] * 3 + g] : 0.f;
-#pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                const int v = n0 + 16 * j + vl;
-                const float* vp = a.resid + (size_t)bdy[i] * a.ldr + 3 * v;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) vpr[i][j][c] = bok && v < a.Nc ? vp[c] : 0.f;
-            }
-        }
+        __syncthreads();   // every wave done reading the ring (the B slots are shared)
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                const int v = n0 + 16 * j + vl;
-                if (g < 3 && bdy[i] * 16 < a.M && v < a.Nc) {
-                    const f32x4 t = acc[i][j];
-                    const float x = fmaf(t[0], vpr[i][j][0], fmaf(t[1], vpr[i][j][1], fmaf(t[2], vpr[i][j][2], t[3])));
-                    a.out[(size_t)bdy[i] * a.ldo + 3 * v + g] = x + tb[i];
+            for (int j = 0; j < FN; ++j)
+                *reinterpret_cast<f32x4*>(Cs + (wave * RW + 16 * i + (lane & 15)) * LDC + 16 * j + 4 * g) = acc[i][j];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int lr = wave * RW + q * RPI + rsub;
+            f32x4 v = *reinterpret_cast<const f32x4*>(Cs + lr * LDC + cl);
+            if (idn) v += xi[q];   // (acc + x) + bias, the order xgemm_pt_kernel keeps too
+            v += bv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (BN == 64 && a.rx) v[e] += xr[q % NQR][0] * rw[e][0] + xr[q % NQR][1] * rw[e][1] + xr[q % NQR][2] * rw[e][2] + xr[q % NQR][3] * rw[e][3];
+                v[e] = v[e] > 0.f ? v[e] : slope * v[e];
+            }
+            if (lr < RT && r0 + lr < a.M) {
+                if (cok) {
+                    xst4(outp + (size_t)(r0 + lr) * a.ldo + col, v, a.nts);
+                } else {
+                    for (int e = 0; e < 4 && col + e < a.Nc; ++e) {
+                        float t = *(Cs + lr * LDC + cl + e) + (a.bias ? a.bias[col + e] : 0.f);
+                        if (a.rx)
+                            for (int c = 0; c < a.rxc; ++c) t = fmaf(xr[q % NQR][c], a.rw[(col + e) * a.rxc + c], t);
+                        outp[(size_t)(r0 + lr) * a.ldo + col + e] = t > 0.f ? t : slope * t;
+                    }
                 }
             }
+        }
     } else {
         // ---- EPI_GRAPH: the C tile through LDS, then the graph mix per frame
         float* Cs = reinterpret_cast<float*>(smem);
@@ -664,16 +489,18 @@ __global__ __launch_bounds__(64 * NW_, NW_ == 8 ? 1 : 2) void xgemm_kernel(XArgs
 // stores them row-major (whole 128-B lines). Rows past M store to a_trash, so
 // every wave issues the same count of vector-memory ops per tile and the
 // vmcnt waits stay exact. Same arithmetic, in the same order, as
-// xgemm_kernel with the LDS epilogue: bit-identical output.
-// EPI: EPI_BIAS (temporal convs) or EPI_SKIN (SMPL-X skinning, the epilogue
-// of xgemm_kernel's EPI_SKIN from registers, non-transposed MFMA);
+// xgemm_kernel's EPI_BIAS epilogue: bit-identical output.
+// EPI: EPI_BIAS (temporal convs) or EPI_SKIN (SMPL-X skinning from the
+// registers, non-transposed MFMA: rows = body * skin_rows + entry of T_v(b) =
+// sum_j W[v][j] A_j(b), columns = vertices; verts[b][3v + k] = T[k][:3] .
+// v_posed[b][3v..] + T[k][3] + transl[b][k], the fma chain of cgemm.hip's EPI_SKIN);
 // IDN: identity residual (block input rows); RX: layer 0's residual conv rows
 template <int BN, int EPI, bool IDN, bool RX>
 __global__ __launch_bounds__(256, 2) void xgemm_pt_kernel(XArgs a) {
     constexpr bool SKIN = EPI == EPI_SKIN;
     using C = XCfg<BN, EPI_BIAS, 4>;   // the same ring (EPI_SKIN needs no C tile)
     constexpr int NW = 4, FM = C::FM, FN = C::FN, NIA = C::NIA, NIBW = C::NIBW, RW = C::RW, BM = C::BM;
-    static_assert(C::NIB_TOT % NW == 0 && C::LB == 1 && C::NSA == 2 && C::NSB == 2, "pt pipeline");
+    static_assert(C::NW == NW && C::LB == 1 && C::NSA == 2 && C::NSB == 2, "pt pipeline");
     constexpr int LDC = BN + 4, LPR = BN / 4, RPI = 64 / LPR, NQ = 8 / RPI;   // staging: 8 rows per quarter
     static_assert(9 * LDC * 4 * NW <= C::BBYTES, "staging (8 rows + a dummy row per wave) fits one B slot");
     __shared__ __attribute__((aligned(16))) unsigned char smem[C::SMEM];
@@ -692,9 +519,7 @@ __global__ __launch_bounds__(256, 2) void xgemm_pt_kernel(XArgs a) {
     // tile i of this workgroup -> (first row, column tile): XCD-aware order over
     // the linear id b + i G (G % 8 == 0: the XCD of the id is the workgroup's)
     auto tile_of = [&](int i, int& r0, int& nt) __attribute__((always_inline)) {
-        const int L = b + i * G;
-        const int per = ntot >> 3, rem = ntot & 7, x = L & 7, k = L >> 3;
-        const int swz = x < rem ? x * (per + 1) + k : rem * (per + 1) + (x - rem) * per + k;
+        const int swz = xcd_slot(b + i * G, ntot);
         r0 = (swz / ntn) * BM;
         nt = swz - (swz / ntn) * ntn;
     };
@@ -705,8 +530,7 @@ __global__ __launch_bounds__(256, 2) void xgemm_pt_kernel(XArgs a) {
 #pragma unroll
     for (int j = 0; j < NIA; ++j) {
         const int rr = (wave * NIA + j) * 8 + (lane >> 3);
-        const int pl = (lane & 7) ^ xa_swz(rr);
-        a_uo[j] = 32 * (pl & 3) + 16 * (pl >> 2);
+        a_uo[j] = xa_dma_unit(rr, lane);
     }
     auto set_rows = [&](int r0) __attribute__((always_inline)) {
 #pragma unroll
@@ -857,11 +681,8 @@ __global__ __launch_bounds__(256, 2) void xgemm_pt_kernel(XArgs a) {
         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int bsw = (-((lane & 15) >> 2)) & 3;
     const int boff = (lane & 15) * 64 + ((g ^ bsw) << 4);
-    auto mma = [&](const xbf16x8& x, const xbf16x8& w, f32x4& c) __attribute__((always_inline)) {
-        // EPI_BIAS transposed (lane = row (l & 15), 4 channels); EPI_SKIN not (lane = vertex, 4 entries)
-        c = SKIN ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, w, c, 0, 0, 0)
-                 : __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0);
-    };
+    // EPI_BIAS transposed (lane = row (l & 15), 4 channels); EPI_SKIN not (lane = vertex, 4 entries)
+    auto mma = [&](const xbf16x8& x, const xbf16x8& w, f32x4& c) __attribute__((always_inline)) { xmma<!SKIN>(x, w, c); };
     auto read_a = [&](int s, f32x4 (&lo)[FM], f32x4 (&hi)[FM]) __attribute__((always_inline)) {
         const unsigned char* A = a_slot(s & 1);
 #pragma unroll
@@ -1024,29 +845,36 @@ __global__ __launch_bounds__(256, 2) void xgemm_pt_kernel(XArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// What both launches ask of the operands: a tile width, packed weights, one or
+// two segments that the K cursors can pack (cin / 32 and kt in 8 bits each) and
+// the DMA can address, an identity residual that is the output row, and layer
+// 0's residual conv on a 64-column tile
+static bool xgemm_operands_ok(const XArgs& a, int bn) {
+    if ((bn != 64 && bn != 128) || !a.wp || !a.out || a.nseg < 1 || a.nseg > 2) return false;
+    for (int s = 0; s <= a.nseg; ++s) {
+        const XSeg& g = s < a.nseg ? a.seg[s] : a.idn;
+        if (s == a.nseg && !g.src) break;
+        if (!g.src || g.cin % 32 || g.cin / 32 > 255 || g.kt < 1 || g.kt > 255 || g.ld % 4 || g.ld < g.cin ||
+            g.rows_in * g.ld * 4 >= (1LL << 31))
+            return false;
+    }
+    if (a.idn.src && (a.idn.kt != 1 || a.idn.stride != 1 || a.idn.pad != 0 || a.idn.tin != a.tout || a.idn.cin != a.Nc))
+        return false;
+    return !a.rx || (bn == 64 && a.rxc >= 0 && a.rxc <= 4);
+}
+
 hipError_t launch_xgemm_pt(const XArgs& a, int bn, int ncu, hipStream_t st, int epi) {
     if (a.M <= 0 || a.Nc <= 0) return hipSuccess;
-    const int kall = xgemm_kmain(a);
     const bool skin = epi == EPI_SKIN;
     if (epi != EPI_BIAS && !skin) return hipErrorInvalidValue;
     if (skin && (a.skin_rows != 0 && a.skin_rows != 12 && a.skin_rows != 16)) return hipErrorInvalidValue;
     const int srows = skin && a.skin_rows == 12 ? 12 : 16;
     if (skin && (bn != 128 || a.M % srows || !a.resid || a.ldr < 3 * a.Nc || a.ldo < 3 * a.Nc || a.idn.src || a.rx))
         return hipErrorInvalidValue;
-    if ((bn != 64 && bn != 128) || !a.wp || !a.out || !a.trash || !a.bias || (!skin && (a.ldo % 4 || a.Nc % bn)) || a.nseg < 1 || a.nseg > 2 ||
-        kall < 2 || a.ksplit > 1 || (a.nw != 0 && a.nw != 4))
+    if (!xgemm_operands_ok(a, bn) || !a.trash || !a.bias || (!skin && (a.ldo % 4 || a.Nc % bn)) || xgemm_kmain(a) < 2 ||
+        a.ksplit > 1)
         return hipErrorInvalidValue;
-    for (int s = 0; s <= a.nseg; ++s) {
-        const XSeg& g = s < a.nseg ? a.seg[s] : a.idn;
-        if (s == a.nseg && !g.src) break;
-        // the K cursors pack cin/32 and kt into 8 bits each
-        if (!g.src || g.cin % 32 || g.cin / 32 > 255 || g.kt < 1 || g.kt > 255 || g.ld % 4 || g.ld < g.cin ||
-            g.rows_in * g.ld * 4 >= (1LL << 31))
-            return hipErrorInvalidValue;
-    }
-    if (a.idn.src && (a.idn.kt != 1 || a.idn.stride != 1 || a.idn.pad != 0 || a.idn.tin != a.tout || a.idn.cin != a.Nc))
-        return hipErrorInvalidValue;
-    if (a.rx && (bn != 64 || a.Nc != bn || a.rxc < 0 || a.rxc > 4 || !a.rw || a.idn.src)) return hipErrorInvalidValue;
+    if (a.rx && (a.Nc != bn || !a.rw || a.idn.src)) return hipErrorInvalidValue;
     if ((long long)(skin ? a.M / srows : a.M) * a.ldo >= (1LL << 31) * 1LL * 4) return hipErrorInvalidValue;
     const long long ntot = (long long)((a.M + 127) / 128) * ((a.Nc + bn - 1) / bn);
     long long G = std::min<long long>(ntot, 2LL * ncu);
@@ -1066,54 +894,29 @@ hipError_t launch_xgemm_pt(const XArgs& a, int bn, int ncu, hipStream_t st, int 
     return hipGetLastError();
 }
 
-int xgemm_tile_rows(int epi, int nw) {
-    const int bm = 32 * (nw == 8 ? 8 : 4);
-    return epi == EPI_GRAPH ? bm / 17 * 17 : bm;
-}
+int xgemm_tile_rows(int epi) { return epi == EPI_GRAPH ? 128 / 17 * 17 : 128; }
 
 hipError_t launch_xgemm(const XArgs& a, int bn, int epi, hipStream_t st) {
     if (a.M <= 0 || a.Nc <= 0) return hipSuccess;
-    if ((bn != 64 && bn != 128) || (epi != EPI_BIAS && epi != EPI_GRAPH && epi != EPI_SKIN) || !a.wp || !a.out ||
-        (epi != EPI_SKIN && a.ldo % 4) ||
-        a.nseg < 1 || a.nseg > 2 || a.ksteps != xgemm_ksteps(a) || xgemm_kmain(a) <= 0)
+    if ((epi != EPI_BIAS && epi != EPI_GRAPH) || !xgemm_operands_ok(a, bn) || a.ldo % 4 || xgemm_kmain(a) <= 0)
         return hipErrorInvalidValue;
-    for (int s = 0; s <= a.nseg; ++s) {
-        const XSeg& g = s < a.nseg ? a.seg[s] : a.idn;
-        if (s == a.nseg && !g.src) break;
-        // the K cursors pack cin/32 and kt into 8 bits each
-        if (!g.src || g.cin % 32 || g.cin / 32 > 255 || g.kt < 1 || g.kt > 255 || g.ld % 4 || g.ld < g.cin ||
-            g.rows_in * g.ld * 4 >= (1LL << 31))
-            return hipErrorInvalidValue;
-    }
-    if (epi == EPI_GRAPH && (a.V != 17 || a.M % 17 || !a.amix || !a.bias || a.idn.src)) return hipErrorInvalidValue;
-    if (a.rx && (bn != 64 || epi != EPI_BIAS || a.rxc < 0 || a.rxc > 4)) return hipErrorInvalidValue;
-    if (a.idn.src && (a.idn.kt != 1 || a.idn.stride != 1 || a.idn.pad != 0 || a.idn.tin != a.tout || a.idn.cin != a.Nc))
-        return hipErrorInvalidValue;
-    if (epi == EPI_SKIN && (a.M % 16 || (a.skin_rows && a.skin_rows != 16) || !a.resid || a.ldr < 3 * a.Nc || a.ldo < 3 * a.Nc || a.idn.src || a.rx))
-        return hipErrorInvalidValue;
-    if ((long long)(epi == EPI_SKIN ? a.M / 16 : a.M) * a.ldo >= (1LL << 31) * 1LL * 4) return hipErrorInvalidValue;
-    const int nw = 4, rt = xgemm_tile_rows(epi, nw);
-    if (a.nw != 0 && a.nw != 4) return hipErrorInvalidValue;
+    if (epi == EPI_GRAPH && (a.V != 17 || a.M % 17 || !a.amix || !a.bias)) return hipErrorInvalidValue;
+    if (epi != EPI_BIAS && (a.idn.src || a.rx)) return hipErrorInvalidValue;   // the residuals are EPI_BIAS's
+    if ((long long)a.M * a.ldo >= (1LL << 31) * 1LL * 4) return hipErrorInvalidValue;
+    const int rt = xgemm_tile_rows(epi);
     const int ks = a.ksplit > 1 ? a.ksplit : 1;
     if (ks > 1) {   // one kt-1 segment, raw partials, every slice non-empty
         const int kall = xgemm_kmain(a), kper = (kall + ks - 1) / ks;
-        if (epi != EPI_BIAS || a.nseg != 1 || a.seg[0].kt != 1 || a.idn.src || a.rx || a.bias || a.act != ACT_NONE ||
+        if (epi != EPI_BIAS || bn != 128 || a.nseg != 1 || a.seg[0].kt != 1 || a.idn.src || a.rx || a.bias || a.act != ACT_NONE ||
             (ks - 1) * kper >= kall || a.trace)
             return hipErrorInvalidValue;
     }
-    const dim3 grid((a.M + rt - 1) / rt, (a.Nc + bn - 1) / bn, ks), blk(64 * nw);
+    const dim3 grid((a.M + rt - 1) / rt, (a.Nc + bn - 1) / bn, ks), blk(256);
     (void)hipGetLastError();
-#define XL(BN_, EPI_, NW__) hipLaunchKernelGGL((xgemm_kernel<BN_, EPI_, NW__, false>), grid, blk, 0, st, a)
-    if (ks > 1) {
-        if (bn == 128) hipLaunchKernelGGL((xgemm_kernel<128, EPI_BIAS, 4, true>), grid, blk, 0, st, a);
-        else return hipErrorInvalidValue;
-    } else if (epi == EPI_SKIN) {
-        if (bn == 128) XL(128, EPI_SKIN, 4);
-        else XL(64, EPI_SKIN, 4);
-    } else {
-        if (bn == 128) { if (epi == EPI_BIAS) XL(128, EPI_BIAS, 4); else XL(128, EPI_GRAPH, 4); }
-        else { if (epi == EPI_BIAS) XL(64, EPI_BIAS, 4); else XL(64, EPI_GRAPH, 4); }
-    }
+#define XL(BN_, EPI_, SK_) hipLaunchKernelGGL((xgemm_kernel<BN_, EPI_, 4, SK_>), grid, blk, 0, st, a)
+    if (ks > 1) XL(128, EPI_BIAS, true);
+    else if (bn == 128) { if (epi == EPI_BIAS) XL(128, EPI_BIAS, false); else XL(128, EPI_GRAPH, false); }
+    else { if (epi == EPI_BIAS) XL(64, EPI_BIAS, false); else XL(64, EPI_GRAPH, false); }
 #undef XL
     return hipGetLastError();
 }

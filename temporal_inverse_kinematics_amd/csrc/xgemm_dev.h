@@ -1,6 +1,7 @@
 // xgemm_dev.h — device pieces shared by the bf16x3 GEMM kernels (xgemm.hip,
-// xgraph.hip, xblock.hip, xtconv.hip): the fp32 -> three-bf16-plane split, the A-image swizzle, the
-// epilogue store, and the LDS ring geometry of a tile configuration.
+// xgraph.hip, xblock.hip, xtws.hip): the fp32 -> three-bf16-plane split, the
+// A-image swizzle and its DMA unit, the MFMA of one product, the epilogue
+// store, and the LDS ring geometry of xgemm.hip's tile.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,6 +51,22 @@ __device__ __forceinline__ void xst4(float* p, const f32x4 v, bool nt) {
 
 __device__ __forceinline__ int xa_swz(int r) { return (r >> 1) & 7; }
 
+// A DMA: the lane that fills unit lane & 7 of image row rr fetches the logical
+// unit pl = (lane & 7) ^ swz(rr) (g = pl & 3, h = pl >> 2); its byte offset in
+// the row's 128-B K block
+__device__ __forceinline__ int xa_dma_unit(int rr, int lane) {
+    const int pl = (lane & 7) ^ xa_swz(rr);
+    return 32 * (pl & 3) + 16 * (pl >> 2);
+}
+
+// one bf16 MFMA of the bf16x3 product. TR: C^T = W . X^T, so lane l ends with
+// row (l & 15), channels 4 (l >> 4) .. +3; else lane l holds column (l & 15), rows 4 (l >> 4) .. +3
+template <bool TR>
+__device__ __forceinline__ void xmma(const xbf16x8& x, const xbf16x8& w, f32x4& c) {
+    c = TR ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0)
+           : __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, w, c, 0, 0, 0);
+}
+
 // EPI_SKIN: body b and transform row k of a lane's 4 GEMM rows rb .. rb + 3
 // (rb % 4 == 0, so they never straddle bodies). 16 rows per body: k == 3 is
 // the [0 0 0 1] row (not stored); 12 rows per body: the 3x4 part only
@@ -66,10 +83,10 @@ __device__ __forceinline__ void xskin_row(int rb, int srows, int& b, int& k) {
 
 template <int BN, int EPI, int NW_>
 struct XCfg {
-    // NW waves of 32 rows (two 16-row fragments) each: NW = 8 is one 256-row
-    // workgroup per CU (two waves per SIMD); NW = 4 a 128-row workgroup of
-    // <= 80 KB LDS, two per CU, so one workgroup's prologue and epilogue run
+    // NW = 4 waves of 32 rows (two 16-row fragments) each: a 128-row workgroup
+    // of <= 80 KB LDS, two per CU, so one workgroup's prologue and epilogue run
     // under the other's main loop
+    static_assert(NW_ == 4, "one tile shape");
     static constexpr int NW = NW_, NT = 64 * NW, BM = 32 * NW, FM = 2, FN = BN / 16, RW = 32;
     static constexpr bool TR = EPI == EPI_BIAS;   // transposed MFMA: each lane ends with 4 channels of a row
     static constexpr int ABYTES = BM * 128;
@@ -78,22 +95,22 @@ struct XCfg {
     // A rows are DMA'd and consumed by the same wave (wave w fills and reads rows
     // 32w..32w+31), so the A ring needs no barrier: 2 slots, issued 2 steps ahead
     // (a slot is free once its step's fragments were split, one step early).
-    // B (weights) is shared by all waves, one barrier per step: issued LB steps
-    // ahead into NSB = LB + 1 slots (LB = 1 for the two-per-CU tile: its wait for
-    // B(k+1) sits after step k's MFMAs, so the DMA has a whole step to land)
-    static constexpr int LB = NW == 8 ? 2 : 1;
-    static constexpr int NSA = 2, NSB = LB + 1;
+    // B (weights) is shared by all waves, one barrier per step: issued LB = 1 step
+    // ahead into NSB = 2 slots (the wait for B(k+1) sits after step k's MFMAs, so
+    // the DMA has a whole step to land)
+    static constexpr int LB = 1, NSA = 2, NSB = 2;
     static constexpr int RING = NSA * ABYTES + NSB * BBYTES;
     static constexpr int NIA = ABYTES / 1024 / NW;   // A DMA instructions per wave per stage
     static constexpr int NIB_TOT = BBYTES / 1024;
-    static constexpr int NIBW = (NIB_TOT + NW - 1) / NW;   // B DMA instructions per wave per stage (at most)
+    static constexpr int NIBW = NIB_TOT / NW;   // B DMA instructions per wave per stage
     static constexpr int RT = EPI == EPI_GRAPH ? BM / 17 * 17 : BM;   // valid rows per tile (whole frames for the mix)
     static constexpr int LDCG = BN + 4;
     // C tile (+ the bias2 slice for the graph mix)
-    static constexpr int CT = EPI == EPI_GRAPH ? BM * LDCG * 4 + 17 * BN * 4 : (EPI == EPI_SKIN ? 0 : BM * LDCG * 4);
+    static constexpr int CT = EPI == EPI_GRAPH ? BM * LDCG * 4 + 17 * BN * 4 : BM * LDCG * 4;
     static constexpr int SMEM = RING > CT ? RING : CT;
-    static constexpr int WG_PER_CU = NW == 8 ? 1 : 2;
+    static constexpr int WG_PER_CU = 2;
     static_assert(NIA * 1024 * NW == ABYTES && NIA * 8 == RW, "A DMA split");
+    static_assert(NIBW * NW == NIB_TOT, "B DMA split: every wave issues NIBW");
     static_assert(SMEM * WG_PER_CU <= 160 * 1024, "LDS");
 };
 

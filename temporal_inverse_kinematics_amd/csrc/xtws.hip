@@ -122,9 +122,7 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
     const int ntiles = a.M / (V * T) * tpw;
     int t_begin, t_end;
     {   // persistent: a contiguous run of tiles per workgroup, runs ordered per XCD
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int per = nwg >> 3, rem = nwg & 7, x = bid & 7, k = bid >> 3;
-        const int s = x < rem ? x * (per + 1) + k : rem * (per + 1) + (x - rem) * per + k;
+        const int nwg = gridDim.x, s = xcd_slot(blockIdx.x, nwg);
         t_begin = (int)((long long)s * ntiles / nwg);
         t_end = (int)((long long)(s + 1) * ntiles / nwg);
     }

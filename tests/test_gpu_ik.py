@@ -561,3 +561,54 @@ def test_xblock_workspace_all_64_channel_backbone(n, T):
     assert torch.equal(a, b), float((a - b).abs().max())
     ref = orc.backbone(x[:2], sd, layers=layers)
     assert np.abs(a[:2].cpu().numpy() - ref.reshape(a[:2].shape)).max() < TOL
+
+
+_LAYERS_32_96 = [(3, 32, 1), (32, 32, 1), (32, 96, 2), (96, 96, 1)]
+_models_32_96_cache = []
+
+
+def _models_32_96():
+    """(bf16x3 backbone, fp32 backbone, state dict) of the 32/96-channel net, built once."""
+    if not _models_32_96_cache:
+        from temporal_inverse_kinematics_amd import synthetic as syn
+        from temporal_inverse_kinematics_amd.models import StgConfig, StgGcn18, StgLayerConfig
+        A = orc.graph_A("coco", "uniform", 2, 1)
+        sd = syn.ik_state_dict(A, seed=5, layers=_LAYERS_32_96)
+        bsd = {k[len("backbone."):]: torch.from_numpy(v) for k, v in sd.items() if k.startswith("backbone.")}
+        cfg = StgConfig([StgLayerConfig(a, b, s, True) for a, b, s in _LAYERS_32_96], 3)
+        nets = []
+        for prec in ("bf16x3", "fp32"):
+            m = StgGcn18(cfg, {"layout": "coco", "strategy": "uniform", "max_hop": 2, "dilation": 1})
+            r = m.load_state_dict(bsd, strict=False)
+            assert not [k for k in r.missing_keys if "num_batches_tracked" not in k] and not r.unexpected_keys, r
+            m = m.cuda().eval()
+            m.tik_precision = prec
+            nets.append(m)
+        _models_32_96_cache.append((nets[0], nets[1], sd))
+    return _models_32_96_cache[0]
+
+
+@pytest.mark.parametrize("n,T", [(1, 1), (3, 9), (9, 16)])
+def test_backbone_32_and_96_channels(n, T):
+    """Layer widths that are multiples of 32 but not of 64 run the tiled
+    kernels no default net reaches: the temporal conv on 64-column tiles with
+    a partial last column tile (xgemm_kernel<64, EPI_BIAS>: layer 0's residual
+    conv from the raw keypoints, an identity residual on 32 and on 96
+    channels, a two-segment stride-2 conv 32 -> 96) and the tiled gcn on 32
+    and 96 columns. Rows: 17 (one partial tile), 459 (window edges at T' = 5),
+    2448 (many tiles, a partial last one). Every window against the float64
+    oracle and against the fp32 path (cgemm.hip, an independent kernel)."""
+    from temporal_inverse_kinematics_amd import synthetic as syn
+    bf, fp, sd = _models_32_96()
+    x = syn.synthetic_windows(n, T, seed=n + T)
+    xd = torch.from_numpy(x).cuda()
+    with torch.no_grad():
+        a = bf(xd).cpu().numpy()
+        b = fp(xd).cpu().numpy()
+    assert np.isfinite(a).all() and np.isfinite(b).all()
+    assert a.shape == (n, (T - 1) // 2 + 1, 17 * 96)
+    ref = orc.backbone(x, sd, layers=_LAYERS_32_96).reshape(a.shape)
+    err_o, err_f = np.abs(a - ref).max(), np.abs(a - b).max()
+    print(f"32/96-channel backbone (n={n}, T={T}): max|bf16x3-oracle|={err_o:.3e} max|bf16x3-fp32|={err_f:.3e}")
+    assert err_o < TOL, err_o
+    assert err_f < TOL, err_f
