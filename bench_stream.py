@@ -1,7 +1,11 @@
 """Config #5: streaming sliding-window (stride 1) online IK, hipGraph-captured
 step, per-frame latency (push of one frame -> its solved pose on the host).
 
-    python bench_stream.py [--frames 10000] [--warmup 100] [--win 64]
+    python bench_stream.py [--frames 10000] [--warmup 100] [--win 64] [--refine N [--smooth W]]
+
+--refine N: the stream refines every pose with N Levenberg-Marquardt iterations
+(one more launch in the recorded step, streaming.OnlineIK(refine=N)) against the
+synthetic SMPL-X body; --smooth W also ties it to the previous refined pose.
 
 bench.py --full reuses measure_online() for its "online" key.
 """
@@ -9,7 +13,7 @@ import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def measure_online(frames=10000, warmup=100, win=64, use_graph=True, precision="bf16x3"):
+def measure_online(frames=10000, warmup=100, win=64, use_graph=True, precision="bf16x3", refine=0, smooth=0.0):
     """Push `frames` frames of the sample sequence (noised repeats) one at a
     time through OnlineIK and time each push (frame in -> pose on the host)."""
     import numpy as np
@@ -22,7 +26,11 @@ def measure_online(frames=10000, warmup=100, win=64, use_graph=True, precision="
     rng = np.random.default_rng(0)
     seq = np.concatenate([seq0 + rng.normal(0, 0.01, seq0.shape).astype(np.float32) for _ in range(reps)])[:frames]
     m = synthetic_model(win_size=win, device="cuda", precision=precision)
-    s = OnlineIK(m, use_graph=use_graph)
+    body = None
+    if refine:
+        from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+        body = SMPLX(syn.synthetic_smplx_constants(seed=1), batch_size=1)
+    s = OnlineIK(m, use_graph=use_graph, refine=refine, smplx_model=body, smooth_weight=smooth)
     for i in range(warmup):
         s.push(seq[i % seq.shape[0]])
     s.reset()
@@ -41,7 +49,8 @@ def measure_online(frames=10000, warmup=100, win=64, use_graph=True, precision="
                                    f"{'hipGraph replay' if use_graph else 'eager launches'} per frame"
                                    + (" (one dataflow kernel, only the frames pose row 0 depends on)"
                                       if s.path == "dataflow" else " (layered forward on the whole window)"),
-                       "frames": frames, "warmup": warmup}}
+                       "frames": frames, "warmup": warmup,
+                       **({"refine_iters": refine, "smooth_weight": smooth} if refine else {})}}
 
 
 def main():
@@ -51,8 +60,10 @@ def main():
     ap.add_argument("--win", type=int, default=64)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--precision", default="bf16x3", choices=["bf16x3", "fp32"])
+    ap.add_argument("--refine", type=int, default=0, help="LM iterations per push (0: the plain stream)")
+    ap.add_argument("--smooth", type=float, default=0.0, help="with --refine: the weight of the tie to the previous refined pose")
     a = ap.parse_args()
-    print(json.dumps(measure_online(a.frames, a.warmup, a.win, not a.no_graph, a.precision)))
+    print(json.dumps(measure_online(a.frames, a.warmup, a.win, not a.no_graph, a.precision, a.refine, a.smooth)))
 
 
 if __name__ == "__main__":

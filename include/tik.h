@@ -195,6 +195,30 @@ int tik_stream_push(tik_stream_t s, const float* frame_host, float* pose_host);
  * written to pinned host memory by the kernel; TIK_ONLINE=0 disables it),
  * 0 = the layered IK forward on the whole window (models it cannot run). */
 int tik_stream_path(tik_stream_t s);
+/* Refinement inside the stream: after the IK step, one more launch of
+ * tik_fk_refine's kernel (B = 1, COCO-17 on SMPL-X, see there) refines the pose
+ * the step just solved against the keypoints of its own frame c = count - 1 - h,
+ * read from the device ring. prior = the network's pose; with smooth > 0 the
+ * cost also ties the pose to the previous *refined* pose, the causal
+ * counterpart of tik_lm_solve_chain's smoothness (none for frame 0 and after
+ * tik_stream_reset). It is a separate launch in stream order on the stream's
+ * one private stream: the captured graph stays a linear chain, and
+ * tik_stream_set_refine records it again. The kernel writes the refined pose
+ * and then a done word to pinned host memory; tik_stream_push waits on that word
+ * and returns the refined pose. While the stream is still filling (c < 0) the
+ * pose passes through unrefined. betas_host: tik_fk's nb values or NULL (the
+ * mean shape); joint_w_host: 17 non-negative keypoint weights or NULL (ones);
+ * both are copied. The stream keeps a reference on `fk` (released when
+ * refinement is switched off or the stream destroyed). iters = 0 switches
+ * refinement off (fk and the rest are ignored). Call it between pushes.
+ * TIK_E_INVALID, leaving the stream as it was: iters < 0, mu <= 0, smooth < 0,
+ * lam0 <= 0, a negative weight, a NULL fk, a body model whose COCO-17 joints
+ * the kernel does not take.
+ * tik_stream_raw_pose: the network's own pose of the last push that returned
+ * one (what that push would have returned without refinement), 66 floats. */
+int tik_stream_set_refine(tik_stream_t s, tik_fk_t fk, const float* betas_host, const float* joint_w_host,
+                          int iters, float mu, float smooth, float lam0);
+int tik_stream_raw_pose(tik_stream_t s, float* pose_host);
 /* Debug (TIK_ONLINE_TRACE=1 at create): the last step's per-task timestamps
  * {ticket taken, inputs ready, staged, computed, reduced, stores complete,
  * done, workgroup} (s_memrealtime ticks, 100 MHz; staged .. reduced: gcn and
@@ -496,6 +520,47 @@ int tik_lm_solve_chain(const float* jac, const float* r, const float* prior, con
                        const float* row_w, int row_w_stride, const float* lambda, const int* seq_starts,
                        float mu, float smooth, int F, int S, int m, int n,
                        float* workspace, float* delta, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The whole Levenberg-Marquardt refinement of a frame in one launch (the
+ * fused path of refine.py, and the refinement inside an online stream): one
+ * workgroup per frame, FK, Jacobian, normal equations, Cholesky, candidate and
+ * accept rule all in LDS; only the pose (and optionally the cost row) is
+ * written. Per frame, theta the 66 pose values of joints 0..21 (the other
+ * joints stay at pose_mean), theta0 = prior, thetap = prev:
+ *   r(theta)    = rel(FK keypoints(theta)) - rel(kps)       rel(x) = x - mean of columns 11 and 12
+ *   cost(theta) = 1/2 sum_k w_k |r_k|^2 + 1/2 mu |theta - theta0|^2 + 1/2 smooth |theta - thetap|^2
+ *   (J^T W J + (mu + smooth + lambda) I) delta = -(J^T W r + mu (theta - theta0) + smooth (theta - thetap))
+ * the thetap terms only with prev and smooth > 0. Exactly `iters` iterations
+ * from lambda = lam0: theta + delta is kept where its cost fell (lambda / 3),
+ * else theta stays (3 lambda); a NaN cost or a pivot that is not positive is no
+ * fall, so a frame with a NaN keypoint returns its pose unchanged with a NaN
+ * cost row. poses (B,66) the start; prior (B,66) or NULL (= poses); prev (B,66)
+ * or NULL; kps (B,17,3); betas: row b at betas + b betas_ld (betas_ld = 0: one
+ * row for all frames) or NULL (the mean shape); joint_w: non-negative keypoint
+ * weights, row b at joint_w + b joint_w_ld (0: one row of 17 shared, 17: per
+ * frame) or NULL (ones); all device fp32. sel17 (host): the 17 keypoints as
+ * joint indices, chain joints (< 55) or single-vertex joints (55 .. 55 + 21),
+ * or NULL = COCO-17 on SMPL-X {55,57,56,59,58,16,17,18,19,20,21,1,2,4,5,7,8};
+ * columns 11 and 12 are the root pair. out_poses (B,66); out_cost (B,iters+1)
+ * or NULL: column 0 the start's cost, column i + 1 the kept pose's after
+ * iteration i, never increasing; dbg_jac (B,51,66) and dbg_r (B,51) or NULL:
+ * the first linearisation, rows root-relative (written for any iters). fp32
+ * FMAs in a fixed order, no atomics: a frame's output bits do not depend on B
+ * or on its place in the batch (they are not those of tik_fk_joints_jacobian /
+ * tik_lm_solve: other sum orders). Both skinning table forms of the handle
+ * (the pairs, TIK_FK_SKIN=dense). The selection travels in the kernel
+ * arguments; no workspace, nothing uploaded, stream-ordered. iters = 0 copies
+ * poses and writes cost column 0.
+ * TIK_E_INVALID: null fk / poses / kps / out_poses, B <= 0, iters < 0, mu <= 0
+ * or NaN, smooth < 0 or NaN, lam0 <= 0 or NaN, betas_ld not 0 or >= nb,
+ * joint_w_ld not 0 or 17, a joint index out of range, a landmark of three
+ * vertices or a contour landmark in sel17.
+ * ---------------------------------------------------------------------- */
+int tik_fk_refine(tik_fk_t fk, const float* poses, const float* prior, const float* prev, const float* kps,
+                  const float* betas, int betas_ld, const float* joint_w, int joint_w_ld, const int* sel17, int iters,
+                  float mu, float smooth, float lam0, int B, float* out_poses, float* out_cost, float* dbg_jac,
+                  float* dbg_r, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,27 +11,10 @@
 //                        landmarks and 17 dynamic contour landmarks.
 // The two GEMMs (pose/shape blend shapes; skinning + vertex transform) run on
 // the fp32-MFMA implicit-GEMM kernel (cgemm.hip, CFG_T128x128 / CFG_S128x128).
-#include "fk.h"
-#include "dev_common.h"
+#include "fk_dev.h"
 
 namespace tik {
-
-__device__ inline void rodrigues_smplx(float x, float y, float z, float R[9]) {
-    // smplx lbs.batch_rodrigues: angle = ||v + 1e-8||, rot_dir = v / angle,
-    // R = I + sin K + (1 - cos) K K
-    const float ax = x + 1e-8f, ay = y + 1e-8f, az = z + 1e-8f;
-    const float ang = sqrtf(ax * ax + ay * ay + az * az);
-    const float inv = 1.0f / ang;
-    const float dx = x * inv, dy = y * inv, dz = z * inv;
-    float s, c;
-    sincosf(ang, &s, &c);
-    const float oc = 1.0f - c;
-    const float d2 = dx * dx + dy * dy + dz * dz;
-    // K = [0,-dz,dy; dz,0,-dx; -dy,dx,0];  (K K)_ij = d_i d_j - delta_ij |d|^2
-    R[0] = 1.f + oc * (dx * dx - d2);  R[1] = -s * dz + oc * dx * dy;      R[2] = s * dy + oc * dx * dz;
-    R[3] = s * dz + oc * dx * dy;      R[4] = 1.f + oc * (dy * dy - d2);  R[5] = -s * dx + oc * dy * dz;
-    R[6] = -s * dy + oc * dx * dz;     R[7] = s * dx + oc * dy * dz;      R[8] = 1.f + oc * (dz * dz - d2);
-}
+using fkd::rodrigues_smplx;   // shared with lm_refine.hip
 
 // One wave per body (4 bodies per 256-thread workgroup), lane j = joint j:
 // Rodrigues and the regressed joint of every joint in parallel, then the

@@ -109,13 +109,6 @@ int resolve_selection(const tik_fk* fk, const char* who, const int* sel, int n, 
     return TIK_OK;
 }
 
-// The arguments the three mesh-free kernels share, from the handle (after its workspace is reserved; sel is set).
-void fill_sel_args(const tik_fk* fk, int B, int n_sel, tik::FkSelArgs& k) {
-    k.B = B; k.n_sel = n_sel; k.nextra = fk->nextra; k.nz = fk->dense ? 0 : fk->sp_nz;
-    k.ajt = fk->ajt.p; k.PT = fk->PT.p; k.WT = fk->WT.p; k.nzw = reinterpret_cast<const int2*>(fk->nzw.p);
-    k.pick_v = fk->pick_v.p; k.pick_w = fk->pick_w.p;
-}
-
 // The two Jacobian entry points between their checks and their own kernels: the joints first, on tik_fk_joints itself
 // (its bits, its "fk_chain" / "fk_joints" launches); the workspace, its 1337 floats per body + the entry point's own
 // (include/tik.h); the chain with feat and A_j forced on unless tik_fk_joints ran it so (npick > 0); then k's base.

@@ -35,6 +35,8 @@
 // waiting between workgroups, plain vector stores. fk_dev.h (shared with fk_joints.hip and fk_shape.hip) holds
 // the column of a wave, the decode of a static joint's vertices, the rows of A_k and the two row products; the
 // blend dot product stays here (one 512-k chain, not fk_joints_kernel's eight chunks: other bits).
+#include <type_traits>
+
 #include "fk_dev.h"
 
 namespace tik {
@@ -46,32 +48,8 @@ __global__ __launch_bounds__(64) void fk_jac_pre_kernel(FkJacArgs a) {
     if (!pre_body(a, b, d)) return;   // no barrier below
     const int j = a.dof[d];
     const float* pz = a.pose + ((size_t)b * 55 + j) * 3;
-    const float v[3] = {pz[0] + a.pose_mean[j * 3], pz[1] + a.pose_mean[j * 3 + 1], pz[2] + a.pose_mean[j * 3 + 2]};
-    const float u[3] = {v[0] + 1e-8f, v[1] + 1e-8f, v[2] + 1e-8f};
-    const float t2 = u[0] * u[0] + u[1] * u[1] + u[2] * u[2];
-    float cA, cB, cAp, cBp;   // A, B, A'/t, B'/t
-    if (t2 < 0.25f) {
-        cA = fmaf(t2, fmaf(t2, fmaf(t2, -1.f / 5040.f, 1.f / 120.f), -1.f / 6.f), 1.f);
-        cB = fmaf(t2, fmaf(t2, fmaf(t2, -1.f / 40320.f, 1.f / 720.f), -1.f / 24.f), 0.5f);
-        cAp = fmaf(t2, fmaf(t2, fmaf(t2, 1.f / 45360.f, -1.f / 840.f), 1.f / 30.f), -1.f / 3.f);
-        cBp = fmaf(t2, fmaf(t2, fmaf(t2, 1.f / 453600.f, -1.f / 6720.f), 1.f / 180.f), -1.f / 12.f);
-    } else {
-        const float t = sqrtf(t2);
-        float s, c;
-        sincosf(t, &s, &c);
-        cA = s / t;
-        cB = (1.f - c) / t2;
-        cAp = (t * c - s) / (t * t2);
-        cBp = (t * s - 2.f * (1.f - c)) / (t2 * t2);
-    }
-    const float vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-    // K(v), K(v)^2 = v v^T - |v|^2 I
-    const float K[9] = {0.f, -v[2], v[1], v[2], 0.f, -v[0], -v[1], v[0], 0.f};
-    float K2[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) K2[3 * r + c] = v[r] * v[c] - (r == c ? vv : 0.f);
+    RodDeriv rd;   // fk_dev.h: the coefficients and K(v), K(v)^2, once for the three axes
+    rodrigues_deriv_setup(pz[0] + a.pose_mean[j * 3], pz[1] + a.pose_mean[j * 3 + 1], pz[2] + a.pose_mean[j * 3 + 2], rd);
     float Gp[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, Gj[9];
     auto rot = [&](int k, float* G) __attribute__((always_inline)) {   // the 3x3 part of A_k
         const f32x4* r = ak_rows(a, k, b);
@@ -84,37 +62,19 @@ __global__ __launch_bounds__(64) void fk_jac_pre_kernel(FkJacArgs a) {
     rot(j, Gj);
     if (p >= 0) rot(p, Gp);
     float* o = a.jw + (size_t)d * PD * a.B + b;
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        // dR = A K(e) + A'/t u_a K(v) + B (e v^T + v e^T - 2 v_a I) + B'/t u_a K(v)^2
-        float dR[9];
-        const float ka = cAp * u[ax], kb = cBp * u[ax];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                // K(e_ax)[r][c]: +1 at (ax+2, ax+1), -1 at (ax+1, ax+2) (indices mod 3)
-                const float ke = (r == (ax + 2) % 3 && c == (ax + 1) % 3) ? 1.f : (r == (ax + 1) % 3 && c == (ax + 2) % 3) ? -1.f : 0.f;
-                const float sy = (r == ax ? v[c] : 0.f) + (c == ax ? v[r] : 0.f) - (r == c ? 2.f * v[ax] : 0.f);
-                dR[3 * r + c] = fmaf(kb, K2[3 * r + c], fmaf(cB, sy, fmaf(ka, K[3 * r + c], cA * ke)));
-            }
+    auto axis = [&](auto AX) __attribute__((always_inline)) {
+        constexpr int ax = decltype(AX)::value;
+        float dR[9], om[3];
+        rodrigues_deriv_axis<ax>(rd, dR);
 #pragma unroll
         for (int m = 0; m < 9; ++m) o[(size_t)(9 * ax + m) * a.B] = dR[m];
-        float M[9], W[9];   // M = Gp dR, W = M Gj^T
+        rodrigues_omega(Gp, dR, Gj, om);
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                M[3 * r + c] = row_linear(Gp[3 * r], Gp[3 * r + 1], Gp[3 * r + 2], dR[c], dR[3 + c], dR[6 + c]);
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                W[3 * r + c] = row_linear(M[3 * r], M[3 * r + 1], M[3 * r + 2], Gj[3 * c], Gj[3 * c + 1], Gj[3 * c + 2]);
-        o[(size_t)(27 + 3 * ax) * a.B] = 0.5f * (W[7] - W[5]);
-        o[(size_t)(27 + 3 * ax + 1) * a.B] = 0.5f * (W[2] - W[6]);
-        o[(size_t)(27 + 3 * ax + 2) * a.B] = 0.5f * (W[3] - W[1]);
-    }
+        for (int c = 0; c < 3; ++c) o[(size_t)(27 + 3 * ax + c) * a.B] = om[c];
+    };
+    axis(std::integral_constant<int, 0>{});
+    axis(std::integral_constant<int, 1>{});
+    axis(std::integral_constant<int, 2>{});
 }
 
 // MAXK: skinning entries per vertex at most (16: the pairs; 55: the dense WT rows); JW: columns (waves) per workgroup

@@ -58,7 +58,7 @@ int tik_fk_create(const tik_tensor* tensors, int n_tensors, int flags, tik_fk_t*
 }
 
 int tik_fk_destroy(tik_fk_t handle) {
-    delete handle;   // the one delete of the FK host code: create holds the handle in a unique_ptr
+    if (handle) fk_release(handle);   // freed now, or when the last stream that refines with it is destroyed
     return TIK_OK;
 }
 

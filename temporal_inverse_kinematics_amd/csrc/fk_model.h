@@ -2,10 +2,14 @@
 // the host, then one upload; reserve, profile, the getters) and fk_forward.cpp
 // (the three launch paths).
 #pragma once
+#include <atomic>
+
 #include "common.h"
+#include "fk.h"
 #include "fk_fold.h"
 
 struct tik_fk {
+    std::atomic<int> refs{1};   // the handle + every online-IK stream that refines with it (fk_retain / fk_release)
     int V = 0, F = 0, nb = 0, ne = 0, nlmk = 0, ndyn = 0, nextra = 0, njoints = 0;
     bool contour = false;
     tik_host::DevBuf PT;         // [3V][KP]    (fp32 path)
@@ -54,3 +58,20 @@ struct tik_fk {
     tik_host::Profiler prof;     // per-launch HIP events (tik_fk_profile; bench.py's FK roofline)
     bool profiling = false;
 };
+
+namespace tik_host {
+
+inline void fk_retain(tik_fk* fk) { fk->refs.fetch_add(1); }   // a refining stream keeps its body model alive
+inline void fk_release(tik_fk* fk) {
+    if (fk->refs.fetch_sub(1) == 1) delete fk;
+}
+
+// The arguments the mesh-free kernels share (fk_joints.hip, fk_jacobian.hip, fk_shape.hip, lm_refine.hip), from the
+// handle (after its workspace is reserved; sel is set by the caller).
+inline void fill_sel_args(const tik_fk* fk, int B, int n_sel, tik::FkSelArgs& k) {
+    k.B = B; k.n_sel = n_sel; k.nextra = fk->nextra; k.nz = fk->dense ? 0 : fk->sp_nz;
+    k.ajt = fk->ajt.p; k.PT = fk->PT.p; k.WT = fk->WT.p; k.nzw = reinterpret_cast<const int2*>(fk->nzw.p);
+    k.pick_v = fk->pick_v.p; k.pick_w = fk->pick_w.p;
+}
+
+}  // namespace tik_host

@@ -128,6 +128,7 @@ int alloc_dataflow(tik_stream* s, const OnlineModelView& v, const sp::Plan& p, c
     a.w0 = v.w0; a.b0 = v.b0; a.w3 = v.w3; a.b3 = v.b3;
     a.feat = v.shape.feat; a.hidden = v.shape.hidden; a.pose_dim = v.shape.pose_dim;
     a.hpart = act(p.hpart); a.pose = act(p.pose);
+    s->onl_pose = a.pose;
     if ((rc = device_view(&a.frame, s->host_frame)) || (rc = device_view(&a.pose_host, s->host_pose)) ||
         (rc = device_view(&a.done_host, s->host_done)))
         return rc;
@@ -146,6 +147,11 @@ int alloc_dataflow(tik_stream* s, const OnlineModelView& v, const sp::Plan& p, c
 }
 
 int capture_step(tik_stream* s) {
+    // a step recorded before (tik_stream_set_refine records again): idle by now, its graph goes
+    if (s->exec) HIP_TRY(hipGraphExecDestroy(s->exec));
+    if (s->graph) HIP_TRY(hipGraphDestroy(s->graph));
+    s->exec = nullptr;
+    s->graph = nullptr;
     HIP_TRY(hipStreamBeginCapture(s->st, hipStreamCaptureModeThreadLocal));
     const int rc = stream_record_step(s);
     const hipError_t e = hipStreamEndCapture(s->st, &s->graph);   // the handle owns the graph from here
@@ -218,12 +224,59 @@ int tik_stream_reset(tik_stream_t s) {
         // count restarts at 0: the activations go back to tag 1 (online.hip)
         HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->onl_act.p), ACT_TAG1, s->onl_act.n, s->st));
     }
+    if (s->rhave.p) HIP_TRY(hipMemsetAsync(s->rhave.p, 0, sizeof(int), s->st));   // no previous refined pose
     HIP_TRY(hipStreamSynchronize(s->st));
     s->host_pose[sp::POSE_FLAG] = 0.f;
     *s->host_done = 0;
+    if (s->host_rdone) *s->host_rdone = 0;
     s->pushed = 0;
     s->dcount = 0;
     return TIK_OK;
+}
+
+int tik_stream_set_refine(tik_stream_t s, tik_fk_t fk, const float* betas_host, const float* joint_w_host, int iters, float mu,
+                          float smooth, float lam0) try {
+    if (!s) return fail(TIK_E_INVALID, "tik_stream_set_refine: null stream");
+    // host: a refused setting leaves the stream as it was
+    tik::LmRefineArgs a{};
+    if (iters != 0) {
+        if (int rc = tik::lm_refine_model_args(fk, "tik_stream_set_refine", nullptr, iters, mu, smooth, lam0, a)) return rc;
+        if (joint_w_host)
+            for (int k = 0; k < tik::LMR_COLS; ++k)
+                if (!(joint_w_host[k] >= 0.f))
+                    return fail(TIK_E_INVALID, "tik_stream_set_refine: joint weight %d must be >= 0, got %g", k, (double)joint_w_host[k]);
+    }
+    // device: the stream is idle between pushes; the step is recorded again with or without the extra launch
+    HIP_TRY(hipStreamSynchronize(s->st));
+    const bool graph = s->exec != nullptr;
+    int rc;
+    if (iters != 0) {
+        int* done = nullptr;
+        if ((betas_host && a.nb > 0 && (rc = s->rbetas.upload(std::vector<float>(betas_host, betas_host + a.nb)))) ||
+            (joint_w_host && (rc = s->rjw.upload(std::vector<float>(joint_w_host, joint_w_host + tik::LMR_COLS)))) ||
+            (rc = s->rprev.reserve(tik::LMR_N)) || (rc = s->rhave.reserve(1)) ||
+            (!s->host_refined && (rc = host_alloc(&s->host_refined, tik::LMR_N, hipHostMallocCoherent))) ||
+            (!s->host_rdone && ((rc = host_alloc(&done, 1, hipHostMallocCoherent)) || (s->host_rdone = done, 0))))
+            return rc;
+        HIP_TRY(hipMemsetAsync(s->rhave.p, 0, sizeof(int), s->st));
+        HIP_TRY(hipMemsetAsync(s->rprev.p, 0, sizeof(float) * tik::LMR_N, s->st));
+        HIP_TRY(hipStreamSynchronize(s->st));
+        *s->host_rdone = s->dcount;
+        a.B = 1;
+        a.poses = s->online ? s->onl_pose : s->poses.p;   // the step's device copy of pose row 0 (the dataflow kernel's carries no tag)
+        a.betas = betas_host && a.nb > 0 ? s->rbetas.p : nullptr;
+        a.joint_w = joint_w_host ? s->rjw.p : nullptr;
+        a.st.count = s->count.p; a.st.ring = s->ring.p; a.st.W = s->lim.W; a.st.h = s->lim.h;
+        a.st.prev = s->rprev.p; a.st.have = s->rhave.p;
+        if ((rc = device_view(&a.st.pose_host, s->host_refined)) || (rc = device_view(&a.st.done_host, s->host_rdone))) return rc;
+        fk_retain(fk);
+    }
+    if (s->rfk) fk_release(s->rfk);
+    s->rfk = iters != 0 ? fk : nullptr;
+    s->rargs = a;
+    return graph ? capture_step(s) : TIK_OK;
+} catch (const std::bad_alloc&) {
+    return fail(TIK_E_NOMEM, "tik_stream_set_refine: out of host memory");
 }
 
 int tik_debug_stream_inject_error(tik_stream_t s) {

@@ -4,6 +4,8 @@
 // model.cpp hands a stream: shapes and device pointers, nothing else.
 #pragma once
 #include "common.h"
+#include "fk_model.h"
+#include "lm_refine.h"
 #include "online.h"
 #include "stream_plan.h"
 
@@ -52,6 +54,15 @@ struct tik_stream {
     tik_host::DevArray<unsigned long long> onl_trace;   // TIK_ONLINE_TRACE=1
     std::vector<tik_host::DevHBuf> onl_wtp, onl_wgp;    // per layer: temporal conv / gcn weights as bf16x3 MFMA planes
     std::vector<tik_host::DevBuf> onl_wtf, onl_wgf;     // per layer: the same, fp32, K zero-padded to 32
+    float* onl_pose = nullptr;                     // the dataflow step's device copy of the pose row (inside onl_act; no tag)
+    // the refinement launch that follows either step (tik_stream_set_refine; lm_refine.hip, B = 1)
+    tik_fk_t rfk = nullptr;        // retained while the stream refines with it
+    tik::LmRefineArgs rargs{};     // the launch's arguments; rargs.iters == 0: no refinement
+    tik_host::DevBuf rbetas, rjw, rprev;   // betas (nb), keypoint weights (17), the previous refined pose (66)
+    tik_host::DevIBuf rhave;       // non-zero once rprev holds a pose
+    float* host_refined = nullptr;         // pinned, coherent: the refined pose
+    volatile int* host_rdone = nullptr;    // pinned, coherent: the frame count after each refined step
+    bool refining() const { return rargs.iters > 0; }
     ~tik_stream() {
         if (st) (void)hipStreamSynchronize(st);
         if (exec) (void)hipGraphExecDestroy(exec);
@@ -59,7 +70,10 @@ struct tik_stream {
         if (host_frame) (void)hipHostFree(host_frame);
         if (host_pose) (void)hipHostFree(host_pose);
         if (host_done) (void)hipHostFree(const_cast<int*>(host_done));
+        if (host_refined) (void)hipHostFree(host_refined);
+        if (host_rdone) (void)hipHostFree(const_cast<int*>(host_rdone));
         if (st) (void)hipStreamDestroy(st);
         if (model) tik_host::model_release(model);
+        if (rfk) tik_host::fk_release(rfk);
     }
 };

@@ -19,10 +19,15 @@ namespace sp = tik_stream_plan;
 
 namespace tik_host {
 
+// the refinement of the frame the step just solved: one more launch in stream order, the same kernel as tik_fk_refine
+static int record_refine(tik_stream* s) {
+    return s->refining() ? tik::lm_refine_launch(s->rargs, s->st) : TIK_OK;
+}
+
 int stream_record_step(tik_stream* s) {
     if (s->online) {
         HIP_TRY(tik::launch_online(s->onl_args.p, s->onl_grid, s->st));
-        return TIK_OK;
+        return record_refine(s);
     }
     HIP_TRY(hipMemcpyAsync(s->frame_in.p, s->host_frame, sizeof(float) * sp::FRAME, hipMemcpyHostToDevice, s->st));
     HIP_TRY(tik::launch_stream_push(s->ring.p, s->lim.W, sp::FRAME, s->count.p, s->frame_in.p, s->st));
@@ -30,7 +35,7 @@ int stream_record_step(tik_stream* s) {
     int rc = model_forward_ws(s->model, s->window.p, 1, s->lim.W, s->poses.p, s->st, s->ws, false);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(s->host_pose, s->poses.p, sizeof(float) * sp::POSE_DIM, hipMemcpyDeviceToHost, s->st));
-    return TIK_OK;
+    return record_refine(s);
 }
 
 }  // namespace tik_host
@@ -48,13 +53,15 @@ extern "C" int tik_stream_push(tik_stream_t s, const float* frame_host, float* p
     }
     const int next = tik::stream_next_count(s->dcount, s->lim.W);
     bool seen = false;
-    if (s->online) {
+    if (s->online || s->refining()) {
         // the dataflow kernel's last head task writes the new frame count to pinned
         // host memory after the pose: spin on it (sooner than the completion signal
-        // hipStreamSynchronize waits for); the stream stays ordered for the next step
+        // hipStreamSynchronize waits for); the stream stays ordered for the next step.
+        // A refining stream's last launch does the same with its own word, on either path.
+        volatile int* done = s->refining() ? s->host_rdone : s->host_done;
         const auto t0 = std::chrono::steady_clock::now();
         for (long it = 0;; ++it) {
-            if (*s->host_done == next) { seen = true; break; }
+            if (*done == next) { seen = true; break; }
             if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
         }
     }
@@ -67,6 +74,14 @@ extern "C" int tik_stream_push(tik_stream_t s, const float* frame_host, float* p
                                "(this frame's pose is invalid; the stream stays usable)");
     }
     const int valid = s->pushed > s->lim.h;   // frame pushed-1-h >= 0 solved
-    if (valid && pose_host) memcpy(pose_host, s->host_pose, sizeof(float) * sp::POSE_DIM);
+    if (valid && pose_host) memcpy(pose_host, s->refining() ? s->host_refined : s->host_pose, sizeof(float) * sp::POSE_DIM);
     return valid;
+}
+
+extern "C" int tik_stream_raw_pose(tik_stream_t s, float* pose_host) {
+    if (!s || !pose_host) return fail(TIK_E_INVALID, "tik_stream_raw_pose: bad arguments");
+    if (s->pushed <= s->lim.h) return fail(TIK_E_INVALID, "tik_stream_raw_pose: no push has returned a pose yet");
+    // either step's pose is in pinned host memory before the push that produced it returns
+    memcpy(pose_host, s->host_pose, sizeof(float) * sp::POSE_DIM);
+    return TIK_OK;
 }

@@ -233,6 +233,55 @@ def lm_solve_sum(partial: torch.Tensor, mu: float = 0.0, lam: float = 0.0, prior
 
 
 LM_CHAIN_MAX_N = 96              # include/tik.h, TIK_LM_CHAIN_MAX_N
+REFINE_DOF, REFINE_KPS = 66, 17  # include/tik.h, tik_fk_refine: unknowns and keypoints per frame
+NUM_VERTEX_JOINTS = 21           # joints 55 .. 75 are one vertex each; later ones are landmarks of three
+
+
+def check_refine_scalars(iters, mu, smooth, lam0):
+    """The LM scalars of refine_frames and of a refining OnlineIK: iters >= 0, mu > 0, smooth >= 0, lam0 > 0
+    -> them as (int, float, float, float). ValueError otherwise; neither the library nor the device is touched."""
+    if int(iters) != iters or int(iters) < 0:
+        raise ValueError(f"iters must be an integer >= 0, got {iters}")
+    mu, smooth, lam0 = float(mu), float(smooth), float(lam0)
+    if not mu > 0.0:
+        raise ValueError(f"mu (the prior weight) must be > 0, got {mu}: 17 keypoints do not determine 22 rotations")
+    if not smooth >= 0.0:
+        raise ValueError(f"smooth must be >= 0, got {smooth}")
+    if not lam0 > 0.0:
+        raise ValueError(f"lam0 must be > 0, got {lam0}")
+    return int(iters), mu, smooth, lam0
+
+
+def resolve_refine_select(select, num_joints: int):
+    """The 17 keypoints of refine_frames as joint indices: "coco" or 17 ints, each a chain joint (< 55) or a
+    single-vertex joint (55 .. 75). ValueError otherwise (a landmark of three vertices included)."""
+    sel = resolve_select(select, num_joints)
+    if sel is None or len(sel) != REFINE_KPS:
+        raise ValueError(f"refine_frames needs a selection of {REFINE_KPS} joints ('coco' or indices)")
+    for j in sel:
+        if j >= NUM_POSE_JOINTS + NUM_VERTEX_JOINTS:
+            raise ValueError(f"joint {j} is a landmark of three vertices (or a contour landmark): refine_frames takes "
+                             f"chain joints and single-vertex joints, below {NUM_POSE_JOINTS + NUM_VERTEX_JOINTS}")
+    return sel
+
+
+def _check_refine_tensors(num_betas, poses, kps, betas, prior, prev, joint_weight):
+    """Shapes, dtype and contiguity of refine_frames' tensors -> (B, betas_ld, joint_w_ld). ValueError otherwise."""
+    if poses.dim() != 2 or poses.shape[0] < 1 or poses.shape[1] != REFINE_DOF:
+        raise ValueError(f"poses must be (B >= 1, {REFINE_DOF}), got {tuple(poses.shape)}")
+    B = int(poses.shape[0])
+    if tuple(kps.shape) != (B, REFINE_KPS, 3):
+        raise ValueError(f"kps must be {(B, REFINE_KPS, 3)}, got {tuple(kps.shape)}")
+    for name, t in (("prior", prior), ("prev", prev)):
+        if t is not None and tuple(t.shape) != (B, REFINE_DOF):
+            raise ValueError(f"{name} must be {(B, REFINE_DOF)}, got {tuple(t.shape)}")
+    if betas is not None and tuple(betas.shape) not in ((num_betas,), (B, num_betas)):
+        raise ValueError(f"betas must be {(num_betas,)} or {(B, num_betas)}, got {tuple(betas.shape)}")
+    if joint_weight is not None and tuple(joint_weight.shape) not in ((REFINE_KPS,), (B, REFINE_KPS)):
+        raise ValueError(f"joint_weight must be {(REFINE_KPS,)} or {(B, REFINE_KPS)}, got {tuple(joint_weight.shape)}")
+    _check_f32(poses=poses, kps=kps, betas=betas, prior=prior, prev=prev, joint_weight=joint_weight)
+    return (B, num_betas if betas is not None and betas.dim() == 2 else 0,
+            REFINE_KPS if joint_weight is not None and joint_weight.dim() == 2 else 0)
 
 
 def lm_chain_starts(F: int, seq_starts=None) -> np.ndarray:
@@ -489,6 +538,41 @@ class SMPLX:
                                                             _lib.ptr(joints), _lib.stream_of(fp)),
                    "SMPLX.joints_shape_jacobian")
         return jac, joints
+
+    def refine_frames(self, poses: torch.Tensor, kps: torch.Tensor, betas=None, prior=None, prev=None, joint_weight=None,
+                      iters: int = 10, mu: float = 1e-2, smooth: float = 0.0, lam0: float = 1e-2, select="coco",
+                      debug: bool = False):
+        """The whole Levenberg-Marquardt refinement of B frames in one launch
+        (tik_fk_refine, one workgroup per frame): poses (B,66) the start, kps
+        (B,17,3) -> (poses (B,66), cost (B, iters+1)); with debug=True also the
+        first linearisation (jac (B,51,66), r (B,51)), rows root-relative.
+        cost(theta) = 1/2 sum_k w_k |r_k|^2 + 1/2 mu |theta - prior|^2
+        + 1/2 smooth |theta - prev|^2 (the last term only with prev and smooth >
+        0); refine._lm_loop's accept rule with a frame as the unit, exactly
+        `iters` iterations; the cost row never increases. prior (B,66) or None (=
+        poses), prev (B,66) or None, betas (nb,) or (B,nb) or None (the mean
+        shape), joint_weight (17,) or (B,17) non-negative or None (ones); all
+        contiguous float32 on the device. select: "coco" or 17 joint indices,
+        chain joints or single-vertex joints (columns 11 and 12 the root pair).
+        A frame's bits do not depend on B or on its place in the batch.
+        ValueError before the device is touched: a bad scalar (mu <= 0, smooth <
+        0, lam0 <= 0, iters < 0), a wrong shape, a non-contiguous tensor, a
+        landmark of three vertices in the selection."""
+        iters, mu, smooth, lam0 = check_refine_scalars(iters, mu, smooth, lam0)
+        sel = resolve_refine_select(select, self.num_joints)
+        B, betas_ld, jw_ld = _check_refine_tensors(self.num_betas, poses, kps, betas, prior, prev, joint_weight)
+        _lib.require_gpu(poses, kps, betas, prior, prev, joint_weight)
+        dev = poses.device
+        out = torch.empty((B, REFINE_DOF), device=dev, dtype=torch.float32)
+        cost = torch.empty((B, iters + 1), device=dev, dtype=torch.float32)
+        jac = torch.empty((B, 3 * REFINE_KPS, REFINE_DOF), device=dev, dtype=torch.float32) if debug else None
+        r = torch.empty((B, 3 * REFINE_KPS), device=dev, dtype=torch.float32) if debug else None
+        csel = (_lib.ctypes.c_int * REFINE_KPS)(*sel)
+        _lib.check(_lib.load().tik_fk_refine(self._h, poses.data_ptr(), _lib.ptr(prior), _lib.ptr(prev), kps.data_ptr(),
+                                             _lib.ptr(betas), betas_ld, _lib.ptr(joint_weight), jw_ld, csel, iters, mu, smooth,
+                                             lam0, B, out.data_ptr(), cost.data_ptr(), _lib.ptr(jac), _lib.ptr(r),
+                                             _lib.stream_of(poses)), "SMPLX.refine_frames")
+        return (out, cost, jac, r) if debug else (out, cost)
 
     @property
     def workspace_bytes(self) -> int:

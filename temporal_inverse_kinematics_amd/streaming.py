@@ -9,6 +9,14 @@ run_inference's (within fp32 rounding). The default step is one dataflow
 kernel (csrc/online.hip) over only the frames pose row 0 depends on, its convs
 in bf16x3 MFMA arithmetic (`path == "dataflow"`); TIK_ONLINE=0 selects the
 layered forward over the whole window.
+
+`refine=N` adds N Levenberg-Marquardt iterations per push (one more launch in
+the recorded step: the fused kernel of SMPLX.refine_frames, one workgroup, on
+the frame the step just solved and its own keypoints from the device ring), so
+`push` returns a pose whose FK joints sit on the keypoints; `smooth_weight > 0`
+also ties each refined pose to the previous refined one, the causal
+counterpart of refine.refine_smooth. Nobody has measured a good smooth_weight
+on real detections: there is no tuned default, 0 means no tie.
 """
 from __future__ import annotations
 
@@ -19,8 +27,32 @@ import numpy as np
 from . import _lib
 
 
+def check_refine_args(refine, smplx_model, betas, prior_weight, smooth_weight, lam0, joint_weight):
+    """OnlineIK's refinement arguments -> (iters, mu, smooth, lam0, betas float32 (nb,) or None, weights float32
+    (17,) or None). ValueError for refine > 0 without a body model and for a bad weight; the library is not asked."""
+    from .smplx_fk import REFINE_KPS, check_refine_scalars
+    iters, mu, smooth, lam0 = check_refine_scalars(refine, prior_weight, smooth_weight, lam0)
+    if iters == 0:
+        return 0, mu, smooth, lam0, None, None
+    if smplx_model is None or not hasattr(smplx_model, "_h"):
+        raise ValueError("refine > 0 needs smplx_model, the smplx_fk.SMPLX body whose FK joints are pulled onto the keypoints")
+    b = w = None
+    if betas is not None:
+        b = np.ascontiguousarray(betas, dtype=np.float32)
+        if b.shape != (smplx_model.num_betas,) or not np.isfinite(b).all():
+            raise ValueError(f"betas must be ({smplx_model.num_betas},) finite values, got shape {b.shape}")
+    if joint_weight is not None:
+        w = np.ascontiguousarray(joint_weight, dtype=np.float32)
+        if w.shape != (REFINE_KPS,) or not (w >= 0).all():
+            raise ValueError(f"joint_weight must be ({REFINE_KPS},) non-negative values (COCO order), got shape {w.shape}")
+    return iters, mu, smooth, lam0, b, w
+
+
 class OnlineIK:
-    def __init__(self, model, win_size: Optional[int] = None, use_graph: bool = True):
+    def __init__(self, model, win_size: Optional[int] = None, use_graph: bool = True, refine: int = 0, smplx_model=None,
+                 betas=None, prior_weight: float = 1e-2, smooth_weight: float = 0.0, lam0: float = 1e-2, joint_weight=None):
+        iters, mu, smooth, lam0, b, w = check_refine_args(refine, smplx_model, betas, prior_weight, smooth_weight, lam0,
+                                                          joint_weight)
         reg = getattr(model, "regressor", model)
         self.win_size = int(win_size if win_size is not None else model.hparams.win_size)
         self.h = self.win_size // 2
@@ -48,6 +80,15 @@ class OnlineIK:
         self._optr = self._obuf.ctypes.data_as(_lib._F)
         self._pptr = self._pose.ctypes.data_as(_lib._F)
         self.path = "dataflow" if _lib.check(lib.tik_stream_path(self._s)) == 1 else "layered"
+        self.refine = iters
+        self._raw = np.zeros(66, np.float32)
+        self._have_pose = False
+        if iters > 0:
+            # the stream holds a library reference on the body model too; the copies of betas and weights are its own
+            self._smplx = smplx_model
+            _lib.check(lib.tik_stream_set_refine(self._s, smplx_model._h, None if b is None else b.ctypes.data_as(_lib._F),
+                                                 None if w is None else w.ctypes.data_as(_lib._F), iters, mu, smooth, lam0),
+                       "OnlineIK")
 
     def __del__(self):
         try:
@@ -59,9 +100,19 @@ class OnlineIK:
     def reset(self):
         _lib.check(_lib.load().tik_stream_reset(self._s))
         self._last = None
+        self._have_pose = False
+
+    @property
+    def raw(self) -> Optional[np.ndarray]:
+        """The network's own (66,) pose of the last push that returned one (what it would have returned
+        with refine=0), or None before the first."""
+        if not self._have_pose:
+            return None
+        _lib.check(_lib.load().tik_stream_raw_pose(self._s, self._raw.ctypes.data_as(_lib._F)), "OnlineIK.raw")
+        return self._raw.copy()
 
     def push(self, frame: np.ndarray) -> Optional[np.ndarray]:
-        """frame (17,3) -> the (66,) pose of the frame h pushes back, or None while filling.
+        """frame (17,3) -> the (66,) pose of the frame h pushes back (refined when refine > 0), or None while filling.
         A frame with a NaN or an Inf in it raises ValueError and is not appended: the
         stream goes on as if it had never been offered."""
         f = np.asarray(frame, dtype=np.float32)
@@ -77,6 +128,8 @@ class OnlineIK:
         self._fbuf, self._obuf, self._fptr, self._optr = self._obuf, self._fbuf, self._optr, self._fptr
         if rc < 0:
             _lib.check(rc, "OnlineIK.push")
+        if rc == 1:
+            self._have_pose = True
         return self._pose.copy() if rc == 1 else None
 
     def flush(self):
