@@ -1,7 +1,8 @@
 // dev_common.h — device helpers shared by the gfx950 kernels: vector types,
-// the COCO-17 hop<=2 adjacency mask of the graph mix, direct global->LDS
-// buffer DMA (buffer_load ... lds, out-of-range offsets read zeros), counted
-// vmcnt waits and the LDS barrier.
+// the COCO-17 hop<=2 adjacency mask of the graph mix and the A_eff readlane
+// (xam), layer 0's mix-first gcn, direct global->LDS buffer DMA (buffer_load
+// ... lds, out-of-range offsets read zeros), counted vmcnt waits, the LDS
+// barrier and the XCD-aware work order.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,11 @@ __host__ __device__ constexpr unsigned coco_hop2_mask3(int w) {
                                 0x2A0u,  0x540u,  0xF8E8u, 0x17970u, 0xB820u, 0x15840u, 0xA800u, 0x15000u};
     return m[w];
 }
+// A_eff entry i from the 5 VGPRs that hold it across the wave (lane i % 64 of
+// amv[i / 64]; i compile-time): v_readlane, a wave-uniform scalar operand
+__device__ __forceinline__ float xam(const float (&amv)[5], int i) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, amv[i / 64]), i % 64));
+}
 
 // ---- layer 0's spatial half, mix first: with C0 <= 4 input channels the
 // 17 x 17 graph mix commutes with the 1x1 conv (both linear; the conv bias is
@@ -24,14 +30,14 @@ __host__ __device__ constexpr unsigned coco_hop2_mask3(int w) {
 // channels once per (frame, joint) instead of 64 per output. Shared by the layered
 // kernel (layer0.hip) and the whole-block kernel (xblock.hip), which must agree
 // bit for bit. x4: the frame's 17 data_bn'd keypoints as 4 floats each (4th = 0);
-// amv: A_eff across the wave (lane l of amv[k] = A[64 k + l], v_readlane).
+// amv: A_eff across the wave (lane l of amv[k] = A[64 k + l], xam).
 template <bool SPARSE>
 __device__ __forceinline__ f32x4 l0_mix_in(const float* x4, const float (&amv)[5], int wj) {
     f32x4 u = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int v = 0; v < 17; ++v)
         if (!SPARSE || ((coco_hop2_mask3(wj) >> v) & 1u)) {
-            const float av = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, amv[(v * 17 + wj) / 64]), (v * 17 + wj) % 64));
+            const float av = xam(amv, v * 17 + wj);
             const f32x4 xv = *reinterpret_cast<const f32x4*>(x4 + 4 * v);
             u = f32x4{fmaf(av, xv[0], u[0]), fmaf(av, xv[1], u[1]), fmaf(av, xv[2], u[2]), fmaf(av, xv[3], u[3])};
         }

@@ -24,8 +24,8 @@
 // Weights live in registers for the whole launch (weight-stationary): wave w
 // owns output channels 16 (w & 3) .. +15, its Wt' planes (3 taps x 2 K blocks
 // x 3 planes = 72 VGPRs) and Wg' planes (24) preloaded in the MFMA operand
-// layout by xblock_pack_weights. Same products and K order as the layered
-// xgemm path (bf16x3: the six p_i q_j with i + j <= 2, fp32 accumulation).
+// layout by xblock_pack_weights. Same split, products, K order and mix as the
+// layered path, from the same functions (xgemm_dev.h xsplit4, xmma6, xmix_row).
 // HBM per pixel: block 0 reads 12 B and writes 384 B (was 256 + 12 + 768 B);
 // block 1 reads 384 B and writes 256 B (was 256 x 5 B).
 #include <algorithm>
@@ -88,11 +88,7 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
     const int QO = a.nframes, T = a.T;
     const int ntiles = (QO + F - 1) / F;
     int t_begin, t_end;
-    {   // persistent: a contiguous run of tiles per workgroup, runs ordered per XCD
-        const int nwg = gridDim.x, s = xcd_slot(blockIdx.x, nwg);
-        t_begin = (int)((long long)s * ntiles / nwg);
-        t_end = (int)((long long)(s + 1) * ntiles / nwg);
-    }
+    xtile_run(ntiles, t_begin, t_end);   // persistent
     if (t_begin >= t_end) return;
 
     // ---- weights in registers (MFMA A operand: lane l = output channel 16 cg + (l & 15), K group l >> 4).
@@ -207,13 +203,16 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
 #else
     constexpr bool tr = false;
 #endif
-    unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;   // 6 res reads, 7 barrier + next-tile DMA issue (block 1)
-    auto stamp = [&](int i) __attribute__((always_inline)) {
-        if (tr) {
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            if (i >= 0) ph_[i] += t - tlast;
-            tlast = t;
-        }
+    XPhaseClock<8> clk;   // 6 res reads, 7 barrier + next-tile DMA issue (block 1)
+    auto stamp = [&](int i) __attribute__((always_inline)) { clk.stamp(tr, i); };
+    // channels co .. co + 3 of z image row R: z split into the row's three planes
+    auto put_z = [&](int R, int co, const f32x4 z) __attribute__((always_inline)) {
+        xbf16x4 p0, p1, p2;
+        xsplit4(z, p0, p1, p2);
+        const int u = co >> 3, o = (co & 7) * 2;
+        *reinterpret_cast<xbf16x4*>(zimg + xb_unit(R, 0, u) + o) = p0;
+        *reinterpret_cast<xbf16x4*>(zimg + xb_unit(R, 1, u) + o) = p1;
+        *reinterpret_cast<xbf16x4*>(zimg + xb_unit(R, 2, u) + o) = p2;
     };
     load_wt();
     // the compiler's own wait for the Wt' loads goes here (an opaque use), not
@@ -270,17 +269,8 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
                 auto conv_half = [&](auto w0c, auto w1c) __attribute__((always_inline)) {
                     constexpr int W0 = decltype(w0c)::value, W1 = decltype(w1c)::value;
 #pragma unroll
-                    for (int wj = W0; wj < W1; ++wj) {
-                        const f32x4 z = l0_conv_relu(us[f * V + wj], w, *reinterpret_cast<const f32x4*>(a.bias2 + wj * C + co));
-                        // split into the three planes of z image row f * 17 + wj, channels co .. co + 3
-                        xbf16x8 p0, p1, p2;
-                        xsplit8(z, z, p0, p1, p2);
-                        const int R = f * V + wj, u = co >> 3, o = (co & 7) * 2;
-                        typedef __bf16 xbf16x4 __attribute__((ext_vector_type(4)));
-                        *reinterpret_cast<xbf16x4*>(zimg + xb_unit(R, 0, u) + o) = xbf16x4{p0[0], p0[1], p0[2], p0[3]};
-                        *reinterpret_cast<xbf16x4*>(zimg + xb_unit(R, 1, u) + o) = xbf16x4{p1[0], p1[1], p1[2], p1[3]};
-                        *reinterpret_cast<xbf16x4*>(zimg + xb_unit(R, 2, u) + o) = xbf16x4{p2[0], p2[1], p2[2], p2[3]};
-                    }
+                    for (int wj = W0; wj < W1; ++wj)
+                        put_z(f * V + wj, co, l0_conv_relu(us[f * V + wj], w, *reinterpret_cast<const f32x4*>(a.bias2 + wj * C + co)));
                 };
                 using I0 = std::integral_constant<int, 0>;
                 using I9 = std::integral_constant<int, 9>;
@@ -320,14 +310,7 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
                     const int j = s >> 1, kb = s & 1;
                     if (s + XPF < S1) rd(s + XPF, xb[(s + XPF - S0) % (XPF + 1)]);
                     __builtin_amdgcn_sched_barrier(0);
-                    const xbf16x8(&x)[3] = xb[(s - S0) % (XPF + 1)];
-                    // (w0,x2) (w1,x1) (w2,x0) (w0,x1) (w1,x0) (w0,x0): xgemm's product order
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wg[kb][0], x[2], acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wg[kb][1], x[1], acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wg[kb][2], x[0], acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wg[kb][0], x[1], acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wg[kb][1], x[0], acc[j], 0, 0, 0);
-                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wg[kb][0], x[0], acc[j], 0, 0, 0);
+                    xmma6(wg[kb], xb[(s - S0) % (XPF + 1)], acc[j]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 // exchange: [joint][cg][lane] f32x4 in the z image rows (69.6 KB, below the zero row)
@@ -341,31 +324,13 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
                     if (j < J0 || j >= J1) acc[j] = xch[(j * 4 + cg) * 64 + lane];
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();   // every wave's exchange reads done before the z image writes
-                // graph mix in registers: lane = frame fs, channels cho .. cho + 3, output
-                // joints J0 .. J1 (xgemm.hip xmix_store's order: bias2, then v ascending)
+                // graph mix in registers (xmix_row): lane = frame fs, channels cho .. cho + 3,
+                // output joints J0 .. J1, split into the z image
                 if (fs < FIN) {
                     auto mix_half = [&](auto sparse) __attribute__((always_inline)) {
                         constexpr bool SP = decltype(sparse)::value;
 #pragma unroll
-                        for (int w = J0; w < J1; ++w) {
-                            f32x4 z = *reinterpret_cast<const f32x4*>(b2s + w * C + cho);
-#pragma unroll
-                            for (int v = 0; v < V; ++v)
-                                if (!SP || ((coco_hop2_mask3(w) >> v) & 1u)) {
-                                    const float av = __builtin_bit_cast(
-                                        float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, amv[(v * V + w) / 64]), (v * V + w) % 64));
-                                    z += av * acc[v];
-                                }
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) z[e] = z[e] > 0.f ? z[e] : 0.f;
-                            xbf16x8 p0, p1, p2;
-                            xsplit8(z, z, p0, p1, p2);
-                            const int R = fs * V + w, u = cho >> 3, o = (cho & 7) * 2;
-                            typedef __bf16 xbf16x4 __attribute__((ext_vector_type(4)));
-                            *reinterpret_cast<xbf16x4*>(zimg + xb_unit(R, 0, u) + o) = xbf16x4{p0[0], p0[1], p0[2], p0[3]};
-                            *reinterpret_cast<xbf16x4*>(zimg + xb_unit(R, 1, u) + o) = xbf16x4{p1[0], p1[1], p1[2], p1[3]};
-                            *reinterpret_cast<xbf16x4*>(zimg + xb_unit(R, 2, u) + o) = xbf16x4{p2[0], p2[1], p2[2], p2[3]};
-                        }
+                        for (int w = J0; w < J1; ++w) put_z(fs * V + w, cho, xmix_row<SP>(acc, amv, b2s + w * C + cho, w));
                     };
                     if (a.mix_sparse) mix_half(std::true_type{});
                     else mix_half(std::false_type{});
@@ -394,7 +359,6 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
                     res[b] = f32x4{xp[0], xp[1], xp[2], xp[3]};   // data_bn'd keypoints (residual conv input)
                 } else {
                     const int R = jt * FIN + fo + 1, u = cho >> 3, o = (cho & 7) * 2;
-                    typedef __bf16 xbf16x4 __attribute__((ext_vector_type(4)));
                     const xbf16x4 h0 = *reinterpret_cast<const xbf16x4*>(ximg + xb_xunit(R, jt, 0, u) + o);
                     const xbf16x4 h1 = *reinterpret_cast<const xbf16x4*>(ximg + xb_xunit(R, jt, 1, u) + o);
                     const xbf16x4 h2 = *reinterpret_cast<const xbf16x4*>(ximg + xb_xunit(R, jt, 2, u) + o);
@@ -445,14 +409,7 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
                 if (b >= nblk) break;
                 if (i + ZPF < NS) rdz(i + ZPF, zb[(i + ZPF) % (ZPF + 1)]);
                 __builtin_amdgcn_sched_barrier(0);
-                const xbf16x8(&z)[3] = zb[i % (ZPF + 1)];
-                const xbf16x8(&w)[3] = wt[s % 3][s / 3];
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], z[2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], z[1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2], z[0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], z[1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], z[0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], z[0], acc, 0, 0, 0);
+                xmma6(wt[s % 3][s / 3], zb[i % (ZPF + 1)], acc);
                 __builtin_amdgcn_sched_barrier(0);
                 if (s < 5) continue;
                 // epilogue of block b: lane = pixel p, channels cho .. cho + 3
@@ -470,13 +427,12 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
                         v[e] += res[b][0] * rw[e][0] + res[b][1] * rw[e][1] + res[b][2] * rw[e][2] + res[b][3] * rw[e][3];
                         v[e] = v[e] > 0.f ? v[e] : 0.f;
                     }
-                    xbf16x8 p0, p1, p2;
-                    xsplit8(v, v, p0, p1, p2);
-                    typedef __bf16 xbf16x4 __attribute__((ext_vector_type(4)));
+                    xbf16x4 p0, p1, p2;
+                    xsplit4(v, p0, p1, p2);
                     unsigned short* o = st ? a.out_p3 + row * (3 * C) + cho : reinterpret_cast<unsigned short*>(a.trash);
-                    *reinterpret_cast<xbf16x4*>(o) = xbf16x4{p0[0], p0[1], p0[2], p0[3]};
-                    *reinterpret_cast<xbf16x4*>(o + C) = xbf16x4{p1[0], p1[1], p1[2], p1[3]};
-                    *reinterpret_cast<xbf16x4*>(o + 2 * C) = xbf16x4{p2[0], p2[1], p2[2], p2[3]};
+                    *reinterpret_cast<xbf16x4*>(o) = p0;
+                    *reinterpret_cast<xbf16x4*>(o + C) = p1;
+                    *reinterpret_cast<xbf16x4*>(o + 2 * C) = p2;
                 } else {
                     v += res[b];   // (acc + x) + bias: xgemm's identity-epilogue order
                     v += bv;
@@ -496,7 +452,7 @@ __global__ __launch_bounds__(512, 1) void xblock_kernel(XBlkArgs a) {
     }
     if (tr && lane == 0) {
         unsigned long long* o = a.trace + 24 * (size_t)blockIdx.x + (wave == 4 ? 12 : 0);
-        for (int i = 0; i < 8; ++i) o[i] = ph_[i];
+        clk.store(o);
         o[8] = t_end - t_begin; o[9] = 1;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -48,14 +48,7 @@
 
 namespace tik {
 
-// graph mix of one frame, output joints [W0, W1): z[w] = sum_v A[v][w] y[v] +
-// bias2[w], ReLU, stored. w and v are compile-time, so the sparse COCO
-// pattern unrolls and the A entries are wave-uniform scalar loads.
-// A_eff entry i from the 5 VGPRs that hold it across the wave (lane i % 64 of amv[i / 64])
-__device__ __forceinline__ float xam(const float (&amv)[5], int i) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, amv[i / 64]), i % 64));
-}
-
+// graph mix of one frame, output joints [W0, W1) (xgemm_dev.h xmix_row), stored.
 // bias2 is the tile's [17][BN] slice staged in LDS (a global load between the
 // stores would wait for every store before it: vmcnt counts both)
 template <int W0, int W1, bool SPARSE, int BN>
@@ -63,20 +56,7 @@ __device__ __forceinline__ void xmix_store(const f32x4 (&y)[17], const float (&a
                                            const float* __restrict__ bias2s, int lcol, float* __restrict__ o,
                                            int ldo, bool nt) {
 #pragma unroll
-    for (int w = W0; w < W1; ++w) {
-        f32x4 z = *reinterpret_cast<const f32x4*>(bias2s + w * BN + lcol);
-        if constexpr (SPARSE) {
-#pragma unroll
-            for (int v = 0; v < 17; ++v)
-                if ((coco_hop2_mask3(w) >> v) & 1u) z += xam(amv, v * 17 + w) * y[v];
-        } else {
-#pragma unroll
-            for (int v = 0; v < 17; ++v) z += xam(amv, v * 17 + w) * y[v];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) z[e] = z[e] > 0.f ? z[e] : 0.f;
-        xst4(o + (size_t)w * ldo, z, nt);
-    }
+    for (int w = W0; w < W1; ++w) xst4(o + (size_t)w * ldo, xmix_row<SPARSE>(y, amv, bias2s + w * BN + lcol, w), nt);
 }
 
 // SK: a split-K launch (XArgs::ksplit > 1; its own instantiation, so the

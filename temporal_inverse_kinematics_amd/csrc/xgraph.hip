@@ -20,8 +20,8 @@
 //     wave would split every element again); the planes image is double-
 //     buffered, so step k+1's split runs beside step k's MFMAs, one barrier
 //     per step, across tile boundaries (persistent).
-// Products, K order and mix order as the tiled kernel (bf16x3 six products,
-// fp32 accumulation; bias2 then v ascending): bit-identical poses.
+// Products, K order and mix as the tiled kernel, from the same functions
+// (xgemm_dev.h xsplit4, xmma6, xmix_row): bit-identical poses.
 // Tiles: (16-frame group, pass): a 256-channel output runs as two passes of
 // 128 channels (eight waves x 16). Frames are flattened over windows (a 1x1
 // conv has no temporal taps, so tiles may straddle windows).
@@ -45,11 +45,6 @@ constexpr int PBYTES = PX * PROWB;                   // 52,224
 // p * 4 + (u ^ ((R >> 1) & 3)): conflict-free b128 reads of 16 consecutive rows
 __device__ __forceinline__ int xg_unit(int R, int p, int u) { return R * xg::PROWB + ((p * 4 + (u ^ ((R >> 1) & 3))) << 4); }
 
-__device__ f32x4 tik_llvm_raw_buffer_load_v4f32(i32x4 rsrc, int voffset, int soffset, int aux)
-    __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-
-typedef __bf16 xbf16x4 __attribute__((ext_vector_type(4)));
-
 #ifdef TIK_XTUNE
 #define XG_OFF(bit) (a.tune & (bit))
 #else
@@ -72,11 +67,7 @@ __global__ __launch_bounds__(512, 1) void xgraph_kernel(XGraphArgs a) {
     const int nfg = (QO + FR - 1) / FR;
     const int ntiles = nfg * npass;
     int t_begin, t_end;
-    {   // persistent: a contiguous run of tiles per workgroup, runs ordered per XCD
-        const int nwg = gridDim.x, s = xcd_slot(blockIdx.x, nwg);
-        t_begin = (int)((long long)s * ntiles / nwg);
-        t_end = (int)((long long)(s + 1) * ntiles / nwg);
-    }
+    xtile_run(ntiles, t_begin, t_end);   // persistent
     if (t_begin >= t_end) return;
     const int total = (t_end - t_begin) * NK;   // global K steps of this workgroup
     // tile -> (frame group, pass): passes innermost, so a frame group's x rows
@@ -119,16 +110,7 @@ __global__ __launch_bounds__(512, 1) void xgraph_kernel(XGraphArgs a) {
             const int m = U >> 3, u = U & 7;
             const int R = 16 * (m % V) + m / V;
             xbf16x4 p0, p1, p2;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {   // xsplit8's arithmetic, 4 channels
-                const float x = r[i][e];
-                const __bf16 b0 = (__bf16)x;
-                const float r1 = x - (float)b0;
-                const __bf16 b1 = (__bf16)r1;
-                p0[e] = b0;
-                p1[e] = b1;
-                p2[e] = (__bf16)(r1 - (float)b1);
-            }
+            xsplit4(r[i], p0, p1, p2);
             const int h = (u & 1) * 8;
             *reinterpret_cast<xbf16x4*>(P + xg_unit(R, 0, u >> 1) + h) = p0;
             *reinterpret_cast<xbf16x4*>(P + xg_unit(R, 1, u >> 1) + h) = p1;
@@ -172,15 +154,8 @@ __global__ __launch_bounds__(512, 1) void xgraph_kernel(XGraphArgs a) {
     constexpr bool tr = false;
 #endif
     // phases: 0 barrier, 1 MFMAs j < 4, 2 split, 3 loads, 4 MFMAs j >= 4, 5 epilogue
-    unsigned long long ph_[6] = {0, 0, 0, 0, 0, 0}, tlast = 0, tstart = 0;
-    auto stamp = [&](int i) __attribute__((always_inline)) {
-        if (tr) {
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            if (i >= 0) ph_[i] += t - tlast;
-            else tstart = t;
-            tlast = t;
-        }
-    };
+    XPhaseClock<6> clk;
+    auto stamp = [&](int i) __attribute__((always_inline)) { clk.stamp(tr, i); };
     stamp(-1);
 
     // one K step; KB compile-time so the weights and the prefetch registers are
@@ -207,14 +182,7 @@ __global__ __launch_bounds__(512, 1) void xgraph_kernel(XGraphArgs a) {
             if (j + XPF < V) rd(j + XPF, xb[(j + XPF) % (XPF + 1)]);
             __builtin_amdgcn_sched_barrier(0);
             if (XG_OFF(4)) return;
-            const xbf16x8(&x)[3] = xb[j % (XPF + 1)];
-            // (w0,x2) (w1,x1) (w2,x0) (w0,x1) (w1,x0) (w0,x0): xgemm's product order
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[kb][0], x[2], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[kb][1], x[1], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[kb][2], x[0], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[kb][0], x[1], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[kb][1], x[0], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[kb][0], x[0], acc[j], 0, 0, 0);
+            xmma6(w[kb], xb[j % (XPF + 1)], acc[j]);
             __builtin_amdgcn_sched_barrier(0);
         };
 #pragma unroll
@@ -261,18 +229,15 @@ __global__ __launch_bounds__(512, 1) void xgraph_kernel(XGraphArgs a) {
                 constexpr bool SP = decltype(sparse)::value;
 #pragma unroll
                 for (int wj = 0; wj < V; ++wj) {
-                    f32x4 z = *reinterpret_cast<const f32x4*>(b2s + wj * a.cout + co);
+                    const float* b2 = b2s + wj * a.cout + co;
+                    f32x4 z;
+                    if (XG_OFF(16)) {   // mix off: bias2 + the joint's own y
+                        z = *reinterpret_cast<const f32x4*>(b2) + acc[wj];
 #pragma unroll
-                    for (int v = 0; v < V; ++v)
-                        if (XG_OFF(16)) {
-                            if (v == wj) z += acc[v];
-                        } else if (!SP || ((coco_hop2_mask3(wj) >> v) & 1u)) {
-                            const float av = __builtin_bit_cast(
-                                float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, amv[(v * V + wj) / 64]), (v * V + wj) % 64));
-                            z += av * acc[v];
-                        }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) z[e] = z[e] > 0.f ? z[e] : 0.f;
+                        for (int e = 0; e < 4; ++e) z[e] = z[e] > 0.f ? z[e] : 0.f;
+                    } else {
+                        z = xmix_row<SP>(acc, amv, b2, wj);
+                    }
                     float* o = q < QO ? a.out + ((size_t)q * V + wj) * a.ldo + co : a.trash;
                     if (!XG_OFF(8)) xst4(o, z, a.nts);
                 }
@@ -303,10 +268,9 @@ __global__ __launch_bounds__(512, 1) void xgraph_kernel(XGraphArgs a) {
 #ifdef TIK_XTRACE
     if (tr && lane == 0) {
         unsigned long long* o = a.trace + 16 * (size_t)blockIdx.x + (wave == 4 ? 8 : 0);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) o[i] = ph_[i];
+        clk.store(o);
         o[6] = (unsigned long long)total;
-        o[7] = tlast - tstart;
+        o[7] = clk.tlast - clk.tstart;
     }
 #endif
 }

@@ -10,7 +10,7 @@
 //     taps x 128 input channels (144 VGPRs of bf16 planes, loaded once);
 //   * tile = 8 consecutive frames of one window x 17 joints; per 32-channel K
 //     block the 10-frame HALO (frames f0 - 1 .. f0 + 8, zeros outside the
-//     window) is loaded into registers D blocks ahead and split once,
+//     window) is loaded into registers one block ahead and split once,
 //     cooperatively, into a double-buffered LDS image of bf16 planes, one
 //     barrier per K block; the three taps read it at frame offsets 0, 1, 2 —
 //     each z element is loaded and split once per tile instead of three times;
@@ -32,8 +32,8 @@
 // row pitch, the ds_read_b128 of one (block, tap, plane) is conflict-free in
 // every lane group (lanes of the two joints and the two frame halves land on
 // distinct 4-bank slots).
-// Products as xgemm (bf16x3, six products per K block), fp32 accumulation in
-// the order (K block, tap), XT128's K order: the two are bitwise equal.
+// Split and products as xgemm (xgemm_dev.h xsplit4, xmma6), fp32 accumulation
+// in the order (K block, tap), XT128's K order: the two are bitwise equal.
 // FG (xtws_kernel<.., true>, round 6, the default for L3/L4): each tile's output
 // rows, still in the slots, also go through block l + 1's gcn 1x1 conv + graph
 // mix + BN + ReLU (XTWG; see "FG:" below and DESIGN.md §2a), bit for bit what
@@ -55,47 +55,27 @@ constexpr int IMG = (ROWS + H) * PROWB;       // + the dead joint 17's rows (rea
 constexpr int NB = 9;                         // pixel blocks per tile
 constexpr int NKB = 4;                        // 32-channel K blocks
 constexpr int SLOTS = NB * 16 * 512;          // identity / output staging: 144 pixels x 128 channels (73,728)
-// NW waves, each 16 CB = 128 / NW output channels; per-wave slot 144 x 64 CB B (+ 64: slots 16 banks apart)
-// FG (the fused next-block gcn): + bias2 [17][128] of block l + 1 staged in LDS
-template <int NW, bool FG>
-struct Cfg {
-    static constexpr int CB = 8 / NW, NT = 64 * NW, NLD = (NU + NT - 1) / NT;
-    static constexpr int IDW = SLOTS / NW + 64;
-    static constexpr int B2 = FG ? V * 128 * 4 + 320 * 4 : 0;   // + A_eff [17][17] (padded to 320)
-    static constexpr int SMEM = 2 * IMG + NW * IDW + B2;
-    static constexpr int NGU = F * V * 8;                 // the gcn split's 16-B fp32 units per K block (1088)
-    static constexpr int NLG = (NGU + NT - 1) / NT;       // ... per thread (3, the last partial)
-    static_assert(SMEM <= 160 * 1024, "LDS");
-};
+// 8 waves (two per SIMD), each 16 output channels; per-wave slot 144 x 64 B (+ 64: slots 16 banks apart)
+constexpr int NW = 8, NT = 64 * NW;
+constexpr int NLD = (NU + NT - 1) / NT;       // register loads per lane per K block (3, the last partial)
+constexpr int IDW = SLOTS / NW + 64;
+constexpr int NGU = F * V * 8;                // FG: the gcn split's 16-B fp32 units per K block (1088)
+constexpr int NLG = (NGU + NT - 1) / NT;      // ... per thread (3, the last partial)
+constexpr int XPF = 1;                        // operand read-ahead (items; 2 spills)
+constexpr int MIXW = 7;                       // FG mix: waves 0-3 make joints 0 .. MIXW - 1, waves 4-7 the rest (7: 55 vs 52 hop<=2 terms)
+// Measured and no longer switches (docs/HISTORY.md §7a, the xtws entry):
+//   register prefetch one K block ahead (two: 0.297 vs 0.296 ms, at 256 VGPRs);
+//   the next K block's split units after the midpoint items (early in the block: 2 % slower);
+//   no barrier at a tile's first K block, identity DMA at K block 1 (both at K block 0: 0.5 % slower)
+// FG (the fused next-block gcn): + bias2 [17][128] of block l + 1 and A_eff [17][17] (padded to 320) staged in LDS
+template <bool FG>
+constexpr int SMEM = 2 * IMG + NW * IDW + (FG ? V * 128 * 4 + 320 * 4 : 0);
+static_assert(SMEM<true> <= 160 * 1024, "LDS");
 }  // namespace xw
 
 __device__ __forceinline__ int xw_unit(int jj, int h, int p, int u) {
     return (10 * jj + h) * xw::PROWB + ((p * 4 + (u ^ ((jj & 1) << 1))) << 4);
 }
-
-__device__ f32x4 tik_llvm_raw_buffer_load_v4f32_xw(i32x4 rsrc, int voffset, int soffset, int aux)
-    __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-
-typedef __bf16 xwbf16x4 __attribute__((ext_vector_type(4)));
-
-#ifndef XW_D
-#define XW_D 1     // K blocks of register prefetch
-#endif
-#ifndef XW_SPLIT_AT
-#define XW_SPLIT_AT 0   // split unit i after item: 0 = (2 i + 1) NI / (2 NLD) (midpoints), 1 = i NI / NLD + 1
-#endif
-
-#ifndef XW_EPIBAR
-#define XW_EPIBAR 1   // no barrier at a tile's first K block (the epilogue's serves), identity DMA at K block 1 (0: both at K block 0; 0.5 % slower)
-#endif
-
-#ifndef XW_XPF
-#define XW_XPF 1   // operand read-ahead (items; 2 spills at 8 waves)
-#endif
-
-#ifndef XW_MIXW
-#define XW_MIXW 7   // FG mix: waves 0-3 make joints 0 .. XW_MIXW - 1, waves 4-7 the rest (7: 55 vs 52 hop<=2 terms)
-#endif
 
 #ifdef TIK_XTUNE
 #define XW_OFF(bit) (a.tune & (bit))
@@ -103,16 +83,17 @@ typedef __bf16 xwbf16x4 __attribute__((ext_vector_type(4)));
 #define XW_OFF(bit) false
 #endif
 
-template <int D, int NW, bool FG>
-__global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
+// D (K blocks of register prefetch) and NW (waves) stay in the signature: the profiler
+// labels and the tests look the two instantiations up by their full names
+template <int D, int NW_, bool FG>
+__global__ __launch_bounds__(xw::NT, 1) void xtws_kernel(XTConvArgs a) {
     using namespace xw;
-    using C = Cfg<NW, FG>;
-    constexpr int CB = C::CB, NT = C::NT, NLD = C::NLD, IDW = C::IDW;
-    constexpr int NHD = (NU + NT - 1) / NT;   // FG: halo DMA instructions per wave
+    static_assert(D == 1 && NW_ == 8, "one shape");
+    constexpr int NHD = NLD;   // FG: halo DMA instructions per wave
     // the two planes images and the rest (slots, FG's bias2 + A_eff) as separate LDS objects:
     // the compiler then knows an LDS-DMA into one image cannot alias reads of the other or of
     // the slots, and adds no vmcnt(0) before them
-    __shared__ __attribute__((aligned(16))) unsigned char img0[IMG], img1[IMG], sl[C::SMEM - 2 * IMG];
+    __shared__ __attribute__((aligned(16))) unsigned char img0[IMG], img1[IMG], sl[SMEM<FG> - 2 * IMG];
     auto pimg = [&](int kb) __attribute__((always_inline)) { return (kb & 1) ? img1 : img0; };
 
     int tid = threadIdx.x, lane = tid & 63;
@@ -121,11 +102,7 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
     const int T = a.T, tpw = T / F;
     const int ntiles = a.M / (V * T) * tpw;
     int t_begin, t_end;
-    {   // persistent: a contiguous run of tiles per workgroup, runs ordered per XCD
-        const int nwg = gridDim.x, s = xcd_slot(blockIdx.x, nwg);
-        t_begin = (int)((long long)s * ntiles / nwg);
-        t_end = (int)((long long)(s + 1) * ntiles / nwg);
-    }
+    xtile_run(ntiles, t_begin, t_end);   // persistent
     if (t_begin >= t_end) return;
     const int total = (t_end - t_begin) * NKB;
     // first output row of tile t (window w, frames f0 .. f0 + 7) and its first frame
@@ -141,20 +118,14 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
     constexpr bool tr = false;
 #endif
     // FG phases: 0 T K blocks, 1 T epilogue + out stores, 2 gcn split 0, 3-6 gcn K blocks, 7 y + mix
-    unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
-    auto stamp = [&](int i) __attribute__((always_inline)) {
-        if (tr) {
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            if (i >= 0) ph_[i] += t - tlast;
-            tlast = t;
-        }
-    };
+    XPhaseClock<8> clk;
+    auto stamp = [&](int i) __attribute__((always_inline)) { clk.stamp(tr, i); };
     const i32x4 rZ = buf_rsrc(a.z, (unsigned)((long long)a.M * a.ldz * 4));
     const i32x4 rXI = buf_rsrc(a.x, (unsigned)((long long)a.M * a.ldx * 4));
     // ---- the halo rows of global step s (tile t_begin + s / 4, K block s % 4) into registers.
     // Unit U = NT i + tid: halo row m = U / 8 (frame f0 - 1 + m / 17, joint m % 17), channels 4 (U % 8) ..
     // Every lane issues NLD loads per step (out-of-range offsets read zeros): no branch, exact vmcnt
-    f32x4 rb[D][NLD];
+    f32x4 rb[NLD];   // the K block after the one in the planes image
     auto load_unit = [&](int s, f32x4 (&r)[NLD], int i) __attribute__((always_inline)) {
         const int t = t_begin + s / NKB, kb = s - (s / NKB) * NKB;
         int row0, f0;
@@ -164,31 +135,26 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
         const int fh = f0 - 1 + m / V;
         const bool ok = live && U < NU && fh >= 0 && fh < T && !XW_OFF(1);
         const unsigned off = ok ? (unsigned)((long long)(row0 - V + m) * a.ldz * 4 + kb * 128 + u * 16) : DMA_OOB;
-        r[i] = tik_llvm_raw_buffer_load_v4f32_xw(rZ, (int)off, 0, 0);
+        r[i] = tik_llvm_raw_buffer_load_v4f32(rZ, (int)off, 0, 0);
     };
     auto load = [&](int s, f32x4 (&r)[NLD]) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) load_unit(s, r, i);
     };
     // ---- split registers r (step s) into planes image (s & 1)
+    // channels 4 u .. 4 u + 3 (u = 0 .. 7) of x -> the planes of image P's row (joint jj, halo frame h)
+    auto put_planes = [&](unsigned char* P, int jj, int h, int u, const f32x4 x) __attribute__((always_inline)) {
+        xbf16x4 p0, p1, p2;
+        xsplit4(x, p0, p1, p2);
+        const int hb = (u & 1) * 8;
+        *reinterpret_cast<xbf16x4*>(P + xw_unit(jj, h, 0, u >> 1) + hb) = p0;
+        *reinterpret_cast<xbf16x4*>(P + xw_unit(jj, h, 1, u >> 1) + hb) = p1;
+        *reinterpret_cast<xbf16x4*>(P + xw_unit(jj, h, 2, u >> 1) + hb) = p2;
+    };
     // halo unit U (row m = U / 8: frame m / 17, joint m % 17; channels 4 (U % 8) ..) of x -> planes image P
     auto split_store = [&](unsigned char* P, int U, const f32x4 x) __attribute__((always_inline)) {
-        const int m = U >> 3, u = U & 7;
-        const int h = m / V, jj = m - h * V;
-        xwbf16x4 p0, p1, p2;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {   // xsplit8's arithmetic, 4 channels
-            const __bf16 b0 = (__bf16)x[e];
-            const float r1 = x[e] - (float)b0;
-            const __bf16 b1 = (__bf16)r1;
-            p0[e] = b0;
-            p1[e] = b1;
-            p2[e] = (__bf16)(r1 - (float)b1);
-        }
-        const int hb = (u & 1) * 8;
-        *reinterpret_cast<xwbf16x4*>(P + xw_unit(jj, h, 0, u >> 1) + hb) = p0;
-        *reinterpret_cast<xwbf16x4*>(P + xw_unit(jj, h, 1, u >> 1) + hb) = p1;
-        *reinterpret_cast<xwbf16x4*>(P + xw_unit(jj, h, 2, u >> 1) + hb) = p2;
+        const int m = U >> 3, h = m / V;
+        put_planes(P, m - h * V, h, U & 7, x);
     };
     auto split_unit = [&](int kb, const f32x4 (&r)[NLD], int i) __attribute__((always_inline)) {
         const int U = NT * i + tid;
@@ -216,53 +182,44 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) split_unit(s, r, i);
     };
-    // ---- identity rows of tile t (this wave's 16 CB channels) into the wave's LDS slot,
-    // pixel-major (64 CB B per pixel): instruction k covers pixels 16 k / CB .. (1 KB each)
-    constexpr int PPI = 16 / CB;   // pixels per DMA instruction
+    // ---- identity rows of tile t (this wave's 16 channels) into the wave's LDS slot,
+    // pixel-major (64 B per pixel): instruction k covers pixel block k's 16 pixels (1 KB)
     auto dma_ident = [&](int t) __attribute__((always_inline)) {
         int row0, f0;
         tile_geo(t, row0, f0);
         const bool live = t < t_end;
-        const int pl = lane / (4 * CB), c = lane - pl * (4 * CB);
+        const int pp = lane >> 2, c = lane & 3;
 #pragma unroll
-        for (int k = 0; k < NB * CB; ++k) {
-            const int pix = k * PPI + pl, j = pix >> 4, pp = pix & 15;
+        for (int j = 0; j < NB; ++j) {
             const int jj = 2 * j + (pp >> 3), fi = pp & 7;
             const bool ok = live && jj < V && !XW_OFF(1);
-            const unsigned off = ok ? (unsigned)((long long)(row0 + fi * V + jj) * a.ldx * 4 + (16 * CB * wave + 4 * c) * 4) : DMA_OOB;
-            dma16(rXI, idw + k * 1024, off, 0);
+            const unsigned off = ok ? (unsigned)((long long)(row0 + fi * V + jj) * a.ldx * 4 + (16 * wave + 4 * c) * 4) : DMA_OOB;
+            dma16(rXI, idw + j * 1024, off, 0);
         }
     };
 
-    // weights: [cg][tap * 4 + kb][plane][lane][8] (xblock_pack_weights), this wave's cg = CB wave + cb
-    xbf16x8 w[3 * NKB][CB][3];
+    // weights: [cg][tap * 4 + kb][plane][lane][8] (xblock_pack_weights), this wave's cg = wave
+    xbf16x8 w[3 * NKB][3];
 #pragma unroll
     for (int k = 0; k < 3 * NKB; ++k)
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-                w[k][cb][p] = *reinterpret_cast<const xbf16x8*>(a.wp + ((((size_t)(CB * wave + cb) * 3 * NKB + k) * 3 + p) * 64 + lane) * 8);
+        for (int p = 0; p < 3; ++p)
+            w[k][p] = *reinterpret_cast<const xbf16x8*>(a.wp + ((((size_t)wave * 3 * NKB + k) * 3 + p) * 64 + lane) * 8);
     const int g = lane >> 4, px = lane & 15;
-    f32x4 bv[CB];
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb) bv[cb] = *reinterpret_cast<const f32x4*>(a.bias + 16 * (CB * wave + cb) + 4 * g);
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + 16 * wave + 4 * g);
     // FG: block l + 1's bias2 [17][128] and A_eff in LDS (read by the mix, after many barriers)
     float* const b2s = reinterpret_cast<float*>(sl + NW * IDW);
     if constexpr (FG)
         for (int i = tid; i < V * 128 + 320; i += NT) b2s[i] = i < V * 128 ? a.bias2[i] : (i - V * 128 < V * V ? a.amix[i - V * 128] : 0.f);
 
-    // prologue: step 0 -> planes[0]; steps 1 .. D into registers
-    load(0, rb[0]);
-    split(0, rb[0]);
-#pragma unroll
-    for (int d = 1; d <= D; ++d) load(d, rb[d % D]);
+    // prologue: step 0 -> planes[0]; step 1 into registers
+    load(0, rb);
+    split(0, rb);
+    load(1, rb);
 
-    f32x4 acc[NB][CB];
+    f32x4 acc[NB];
 #pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) acc[j][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NB; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // ---- FG: block l + 1's gcn (1x1 conv 128 -> 128 + graph mix + bias2 + ReLU,
     // st_gcn_aaai18.py:211, gconv_origin.py:56-65) on the tile's output rows, which the
@@ -296,26 +253,11 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
     };
     auto gsplit_unit = [&](int kb, int i) __attribute__((always_inline)) {
         const int U = NT * i + tid;
-        if ((i + 1 < C::NLG || U < C::NGU) && !XW_OFF(32)) {
+        if ((i + 1 < NLG || U < NGU) && !XW_OFF(32)) {
             const int m = U >> 3, u = U & 7;
             const int f = m / V, jj = m - f * V;
             const int pix = 16 * (jj >> 1) + 8 * (jj & 1) + f;
-            const f32x4 x = *reinterpret_cast<const f32x4*>(sl + (2 * kb + (u >> 2)) * IDW + pix * 64 + (u & 3) * 16);
-            xwbf16x4 p0, p1, p2;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {   // xsplit8's arithmetic, 4 channels
-                const __bf16 b0 = (__bf16)x[e];
-                const float r1 = x[e] - (float)b0;
-                const __bf16 b1 = (__bf16)r1;
-                p0[e] = b0;
-                p1[e] = b1;
-                p2[e] = (__bf16)(r1 - (float)b1);
-            }
-            unsigned char* P = pimg(kb);
-            const int hb = (u & 1) * 8;
-            *reinterpret_cast<xwbf16x4*>(P + xw_unit(jj, f + 1, 0, u >> 1) + hb) = p0;
-            *reinterpret_cast<xwbf16x4*>(P + xw_unit(jj, f + 1, 1, u >> 1) + hb) = p1;
-            *reinterpret_cast<xwbf16x4*>(P + xw_unit(jj, f + 1, 2, u >> 1) + hb) = p2;
+            put_planes(pimg(kb), jj, f + 1, u, *reinterpret_cast<const f32x4*>(sl + (2 * kb + (u >> 2)) * IDW + pix * 64 + (u & 3) * 16));
         }
     };
     // K block kb's MFMAs (image kb & 1, weights wk); beside(j) runs after item j
@@ -323,7 +265,6 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
         asm volatile("" : "+v"(tid), "+v"(lane));
         const int g = lane >> 4, px = lane & 15, jb = px >> 3, fb = px & 7;
         const unsigned char* P = pimg(kb);
-        constexpr int XPF = XW_XPF;
         xbf16x8 xr[XPF + 1][3];
         auto rd = [&](int j, xbf16x8 (&d)[3]) __attribute__((always_inline)) {
 #pragma unroll
@@ -335,18 +276,11 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
         for (int j = 0; j < NB; ++j) {
             if (j + XPF < NB) rd(j + XPF, xr[(j + XPF) % (XPF + 1)]);
             __builtin_amdgcn_sched_barrier(0);
-            const xbf16x8(&x)[3] = xr[j % (XPF + 1)];
             if (XW_OFF(16)) {
                 beside(j);
                 continue;
             }
-            // (w0,x2) (w1,x1) (w2,x0) (w0,x1) (w1,x0) (w0,x0): xgraph's product order
-            acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[0], x[2], acc[j][0], 0, 0, 0);
-            acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[1], x[1], acc[j][0], 0, 0, 0);
-            acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[2], x[0], acc[j][0], 0, 0, 0);
-            acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[0], x[1], acc[j][0], 0, 0, 0);
-            acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[1], x[0], acc[j][0], 0, 0, 0);
-            acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[0], x[0], acc[j][0], 0, 0, 0);
+            xmma6(wk, xr[j % (XPF + 1)], acc[j]);
             __builtin_amdgcn_sched_barrier(0);
             beside(j);
         }
@@ -355,7 +289,7 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
     auto spread = [&](int kb) __attribute__((always_inline)) {
         return [&, kb](int j) __attribute__((always_inline)) {
 #pragma unroll
-            for (int i = 0; i < C::NLG; ++i)
+            for (int i = 0; i < NLG; ++i)
                 if (j == 3 * i + 1) {
                     gsplit_unit(kb, i);
                     __builtin_amdgcn_sched_barrier(0);
@@ -371,7 +305,7 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
         asm volatile("" : "+v"(tid), "+v"(lane));   // lane-derived addresses made here, not hoisted out of the tile loop
         load_wg(0, wga);
 #pragma unroll
-        for (int i = 0; i < C::NLG; ++i) gsplit_unit(0, i);
+        for (int i = 0; i < NLG; ++i) gsplit_unit(0, i);
         lds_barrier();   // K block 0's planes landed
         stamp(2);
         gmma(0, wga, spread(1));
@@ -400,17 +334,17 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
             const int g = lane >> 4, px = lane & 15;
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
-                *reinterpret_cast<f32x4*>(idw + (16 * j + px) * 64 + g * 16) = acc[j][0];
-                acc[j][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+                *reinterpret_cast<f32x4*>(idw + (16 * j + px) * 64 + g * 16) = acc[j];
+                acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
         lds_barrier();   // y complete; every image read done
         stamp(6);
-        // the mix: thread (frame f, channels 4 c4 ..), waves 0-3 joints 0 .. XW_MIXW - 1, 4-7 the
-        // rest (the COCO hop <= 2 terms split about evenly: 55 / 52 at 7)
+        // the mix (xmix_row): thread (frame f, channels 4 c4 ..), waves 0-3 joints 0 .. MIXW - 1,
+        // 4-7 the rest (the COCO hop <= 2 terms split about evenly: 55 / 52 at 7)
         asm volatile("" : "+v"(tid), "+v"(lane));
         const int it = tid & 255, f = it >> 5, c4 = it & 31;
-        // A_eff across the wave from LDS (5 VGPRs, v_readlane as xgraph.hip)
+        // A_eff across the wave from LDS (5 VGPRs, xam)
         float amv[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k) amv[k] = b2s[V * 128 + 64 * k + lane];
@@ -427,22 +361,11 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
                 if ((need >> v) & 1u)
                     y[v] = *reinterpret_cast<const f32x4*>(sl + (c4 >> 2) * IDW + (16 * (v >> 1) + 8 * (v & 1) + f) * 64 + (c4 & 3) * 16);
 #pragma unroll
-            for (int wj = W0; wj < W1; ++wj) {
-                f32x4 z = *reinterpret_cast<const f32x4*>(b2s + wj * 128 + 4 * c4);
-#pragma unroll
-                for (int v = 0; v < V; ++v)
-                    if (!SP || ((coco_hop2_mask3(wj) >> v) & 1u)) {
-                        const float av = __builtin_bit_cast(
-                            float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, amv[(v * V + wj) / 64]), (v * V + wj) % 64));
-                        z += av * y[v];
-                    }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) z[e] = z[e] > 0.f ? z[e] : 0.f;
-                xst4(a.zout + (size_t)(row0 + f * V + wj) * a.ldzo + 4 * c4, z, a.nts);
-            }
+            for (int wj = W0; wj < W1; ++wj)
+                xst4(a.zout + (size_t)(row0 + f * V + wj) * a.ldzo + 4 * c4, xmix_row<SP>(y, amv, b2s + wj * 128 + 4 * c4, wj), a.nts);
         };
         using I0 = std::integral_constant<int, 0>;
-        using I9 = std::integral_constant<int, XW_MIXW>;
+        using I9 = std::integral_constant<int, MIXW>;
         using I17 = std::integral_constant<int, 17>;
         if (XW_OFF(64)) {
         } else if (wave >= NW / 2) {
@@ -455,9 +378,9 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
         // the next tile's K block 1 into rb (split late in its K block 0); then its K block 0,
         // in place: every thread reads its raw units of image 0, a barrier, then writes their
         // planes into image 0 (the next tile's K block 0 barrier publishes them). This wave's
-        // DMA is older than its z stores (>= min(XW_MIXW, 17 - XW_MIXW)) and those rb loads (NLD)
-        load(s + 2, rb[0]);
-        wait_vm<NLD + (XW_MIXW < V - XW_MIXW ? XW_MIXW : V - XW_MIXW)>();
+        // DMA is older than its z stores (>= min(MIXW, 17 - MIXW)) and those rb loads (NLD)
+        load(s + 2, rb);
+        wait_vm<NLD + (MIXW < V - MIXW ? MIXW : V - MIXW)>();
         lds_barrier();
         asm volatile("" : "+v"(tid), "+v"(lane));
         // (units past NU read inside image 0 and are not used)
@@ -473,21 +396,15 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
         stamp(7);
     };
 
-    // one K block; KB compile-time so the weights and the prefetch registers are statically indexed
+    // one K block; KB compile-time so the weights are statically indexed
     auto step = [&](int s, int t, auto KBc) __attribute__((always_inline)) {
         constexpr int kb = decltype(KBc)::value;
-        constexpr int nb = (kb + 1) % D;   // registers holding step s+1 (s % D == kb % D: 4 % D == 0)
         asm volatile("" : "+v"(tid), "+v"(lane));   // lane-derived addresses: not hoisted across steps
-        // every wave's split(s) landed; every wave done with step s-1's image (the one split(s+1) writes)
-#if XW_EPIBAR
-        // at a tile's first K block the previous tile's epilogue barrier (after this image's
+        // every wave's split(s) landed; every wave done with step s-1's image (the one split(s+1) writes).
+        // At a tile's first K block the previous tile's epilogue barrier (after this image's
         // split and the last reads of the other one) already holds, except at the run's start
         if (kb != 0 || t == t_begin || FG) lds_barrier();
-        constexpr int KDMA = 1;
-#else
-        lds_barrier();
-        constexpr int KDMA = 0;
-#endif
+        constexpr int KDMA = 1;   // the K block that issues the identity DMA
         if constexpr (kb == KDMA) {
             // this tile's identity rows into the wave's slot (every wave is done with the
             // previous tile's outputs there: the barrier above)
@@ -498,7 +415,7 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
         const unsigned char* P = pimg(kb);   // s & 1 == kb & 1 (4 K blocks per tile)
         const int jb = px >> 3, fb = px & 7;
         // operand ring over the 27 (block, tap) items: item n + XPF's planes are read while item n's MFMAs run
-        constexpr int NI = NB * 3, XPF = XW_XPF;
+        constexpr int NI = NB * 3;
         xbf16x8 xr[XPF + 1][3];
         auto rd = [&](int n, xbf16x8 (&d)[3]) __attribute__((always_inline)) {
             const int j = n / 3, tap = n - 3 * (n / 3);
@@ -513,25 +430,14 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
             __builtin_amdgcn_sched_barrier(0);
             if (XW_OFF(4)) return;
             const int j = n / 3, tap = n - 3 * (n / 3);
-            const xbf16x8(&x)[3] = xr[n % (XPF + 1)];
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                const xbf16x8(&wk)[3] = w[tap * NKB + kb][cb];
-                // (w0,x2) (w1,x1) (w2,x0) (w0,x1) (w1,x0) (w0,x0): xgemm's product order
-                acc[j][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[0], x[2], acc[j][cb], 0, 0, 0);
-                acc[j][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[1], x[1], acc[j][cb], 0, 0, 0);
-                acc[j][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[2], x[0], acc[j][cb], 0, 0, 0);
-                acc[j][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[0], x[1], acc[j][cb], 0, 0, 0);
-                acc[j][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[1], x[0], acc[j][cb], 0, 0, 0);
-                acc[j][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wk[0], x[0], acc[j][cb], 0, 0, 0);
-            }
+            xmma6(w[tap * NKB + kb], xr[n % (XPF + 1)], acc[j]);
             if (unit >= 0) {
                 // a split unit after the item's MFMAs in program order, its VALU then
                 // scheduled between them (its LDS writes and load anywhere)
-                if (!XW_OFF(2)) split_unit(kb + 1, rb[nb], unit);
-                if (LDN) load_unit(s + 1 + D, rb[nb], unit);
+                if (!XW_OFF(2)) split_unit(kb + 1, rb, unit);
+                if (LDN) load_unit(s + 2, rb, unit);
 #pragma unroll
-                for (int q = 0; q < 6 * CB; ++q) {
+                for (int q = 0; q < 6; ++q) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
                 }
@@ -549,9 +455,8 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
             int unit = -1;
 #pragma unroll
             for (int i = 0; i < NLD; ++i)
-                // FG K block 0: its rb was loaded just before the tile, so its split units go late
-                if (SPL && n == (FG && kb == 0 ? NI / 2 + (i * NI) / (2 * NLD) : XW_SPLIT_AT ? i * NI / NLD + 1 : ((2 * i + 1) * NI) / (2 * NLD)) + 1)
-                    unit = i;
+                // after the midpoint items; FG K block 0: its rb was loaded just before the tile, so its split units go late
+                if (SPL && n == (FG && kb == 0 ? NI / 2 + (i * NI) / (2 * NLD) : ((2 * i + 1) * NI) / (2 * NLD)) + 1) unit = i;
             mfma_n(n, unit);
         }
         if constexpr (kb == NKB - 1) {
@@ -564,17 +469,15 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
                 wait_vm<(NKB - KDMA) * NLD>();
             }
 #pragma unroll
-            for (int j = 0; j < NB; ++j)
+            for (int j = 0; j < NB; ++j) {
+                f32x4* sl = reinterpret_cast<f32x4*>(idw + (16 * j + px) * 64 + g * 16);
+                f32x4 v = acc[j] + *sl;
+                v += bv;
 #pragma unroll
-                for (int cb = 0; cb < CB; ++cb) {
-                    f32x4* sl = reinterpret_cast<f32x4*>(idw + (16 * j + px) * (64 * CB) + (4 * cb + g) * 16);
-                    f32x4 v = acc[j][cb] + *sl;
-                    v += bv[cb];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-                    *sl = v;   // the output replaces the identity in the slot
-                    acc[j][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
+                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+                *sl = v;   // the output replaces the identity in the slot
+                acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
             // whole output rows from the slots: 32 lanes x 16 B = one 512-B row
             lds_barrier();
             int row0, f0;
@@ -583,8 +486,7 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
             for (int i = 0; i < NB * 16 * 32 / NT; ++i) {
                 const int q = tid + NT * i, pix = q >> 5, cu = q & 31;
                 const int j = pix >> 4, pp = pix & 15, jj = 2 * j + (pp >> 3);
-                const int ws = cu / (4 * CB), pc = cu - ws * (4 * CB);
-                const f32x4 v = *reinterpret_cast<const f32x4*>(sl + ws * IDW + pix * (64 * CB) + pc * 16);
+                const f32x4 v = *reinterpret_cast<const f32x4*>(sl + (cu >> 2) * IDW + pix * 64 + (cu & 3) * 16);
                 float* o = jj < V ? a.out + (size_t)(row0 + (pp & 7) * V + jj) * a.ldo + cu * 4 : a.trash + (tid & 255) * 4;
                 if (!XW_OFF(8)) xst4(o, v, a.nts);
             }
@@ -592,8 +494,8 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
     };
     // static priority for the younger half of the workgroup (waves 4-7 lose VALU arbitration
     // to their older SIMD partners on every segment: MI355X_MICROARCH.md, two waves per SIMD):
-    // 0.265 vs 0.272 ms on L3. 8 waves only (the condition must be wave-uniform: readfirstlane)
-    if (NW == 8 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
+    // 0.265 vs 0.272 ms on L3 (the condition must be wave-uniform: readfirstlane)
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
     stamp(-1);
     auto tphase = [&](int t) __attribute__((always_inline)) {
         const int s0 = (t - t_begin) * NKB;
@@ -620,8 +522,7 @@ __global__ __launch_bounds__(64 * NW, 1) void xtws_kernel(XTConvArgs a) {
 #ifdef TIK_XTRACE
     if (tr && lane == 0) {
         unsigned long long* o = a.trace + 16 * (size_t)blockIdx.x + (wave == 4 ? 8 : 0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = ph_[i];
+        clk.store(o);
         if (wave == 0) o[7] |= (unsigned long long)(t_end - t_begin) << 48;
     }
 #endif
@@ -653,8 +554,8 @@ hipError_t launch_xtws(const XTConvArgs& a, int ncu, hipStream_t st) {
         const int ntiles = (int)(c.M / win) * (a.T / xw::F);
         // 8 waves (two per SIMD, 16 channels each); 4 waves of 32 channels (one per SIMD, the weights
         // through AGPRs: v_accvgpr_read before every MFMA group) measured 0.364 vs 0.288 ms
-        if (a.wg) hipLaunchKernelGGL((xtws_kernel<XW_D, 8, true>), dim3(std::min(ntiles, ncu)), dim3(512), 0, st, c);
-        else hipLaunchKernelGGL((xtws_kernel<XW_D, 8, false>), dim3(std::min(ntiles, ncu)), dim3(512), 0, st, c);
+        if (a.wg) hipLaunchKernelGGL((xtws_kernel<1, 8, true>), dim3(std::min(ntiles, ncu)), dim3(512), 0, st, c);
+        else hipLaunchKernelGGL((xtws_kernel<1, 8, false>), dim3(std::min(ntiles, ncu)), dim3(512), 0, st, c);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
