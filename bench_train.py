@@ -1,6 +1,6 @@
 """SURVEY.md §8f row 4 (optimizer half): the IKPoseTrainer training step on the GPU.
 
-    python bench_train.py [--batch 256] [--T 9] [--steps 50] [--warmup 5]
+    python bench_train.py [--batch 256] [--T 9] [--steps 50] [--warmup 5] [--kp-loss W]
 
 Workload: the reference's training defaults (pose_trainer.py:204-230:
 --bs 256 windows, --win_size 9 -> 9-frame windows, 1 output frame, Adam lr
@@ -11,6 +11,10 @@ training windows/s. Algorithmic work per window: forward FLOPs of the
 dense contractions (oracle count, 92.9 MFLOP at T=9) x 3 (forward, input
 gradient, weight gradient). CPU baseline: oracle/train.py (the reference's
 step restated in PyTorch fp32 autograd) on the host, a bounded sample.
+--kp-loss W times the step with the keypoint term at weight W (tik_trainer_step_kp:
+the three synthetic SMPL-X bodies, a random gender per window, target keypoints =
+the bodies' own FK of the target poses) and, alone, the keypoint kernel on the same
+rows; without it the step is the plain one, unchanged.
 """
 import argparse
 import json
@@ -44,6 +48,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eval", action="store_true",
                     help="also time GpuTrainer.validation_step on the same batches, in this process")
+    ap.add_argument("--kp-loss", type=float, default=None, metavar="W",
+                    help="add the keypoint term rel(FK(pred)) vs rel(keypoints) at weight W (>= 0) to the step")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -55,7 +61,12 @@ def main():
     sd = syn.ik_state_dict(m.regressor.backbone.graph.A, seed=0)
     own = m.regressor.state_dict()
     m.regressor.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items() if k in own}, strict=False)
-    tr = GpuTrainer(m, lr=1e-4)
+    kp_on = a.kp_loss is not None
+    bodies = None
+    if kp_on:
+        from temporal_inverse_kinematics_amd.smplx_fk import load_smplx_models
+        bodies = load_smplx_models(None, "cuda", batch_size=a.batch)
+    tr = GpuTrainer(m, lr=1e-4, smplx_models=bodies, kp_weight=a.kp_loss or 0.0)
     B, T = a.batch, a.T
     Tp = T
     for s in m.regressor.backbone.strides:
@@ -63,12 +74,27 @@ def main():
     xs = [torch.from_numpy(syn.synthetic_windows(B, T, seed=50 + i)).cuda() for i in range(4)]
     rng = np.random.default_rng(0)
     ys = [torch.from_numpy(rng.normal(0, 0.5, (B, Tp, 66)).astype(np.float32)).cuda() for _ in range(4)]
+    kw = [{} for _ in range(4)]
+    if kp_on:
+        order = sorted(bodies)
+        for i in range(4):
+            gid = torch.from_numpy(rng.integers(0, len(order), B).astype(np.int32))
+            betas = torch.from_numpy(rng.normal(0, 1, (B, bodies[order[0]].num_betas)).astype(np.float32)).cuda()
+            full = torch.zeros((B * Tp, 55, 3), device="cuda")
+            full[:, :22] = ys[i].reshape(B * Tp, 22, 3)
+            rb = betas.repeat_interleave(Tp, 0).contiguous()
+            kps = torch.zeros((B * Tp, 17, 3), device="cuda")
+            for g, name in enumerate(order):
+                sel = torch.nonzero(gid.cuda().repeat_interleave(Tp) == g).flatten()
+                if len(sel):
+                    kps[sel] = bodies[name].joints(full[sel], rb[sel].contiguous(), select="coco")
+            kw[i] = {"target_keypoints": kps.reshape(B, Tp, 17, 3), "betas": betas, "gender_id": gid}
     for i in range(a.warmup):
-        tr.step(xs[i % 4], ys[i % 4], seed=i)
+        tr.step(xs[i % 4], ys[i % 4], seed=i, **kw[i % 4])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        loss = tr.step(xs[i % 4], ys[i % 4], seed=1000 + i)
+        loss = tr.step(xs[i % 4], ys[i % 4], seed=1000 + i, **kw[i % 4])
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     fl = 3.0 * fwd_flops_per_window(T)
@@ -84,6 +110,25 @@ def main():
                         "frac": round(fl * B / dt / 1e12 / 157.3, 4),
                         "peak_basis": "dense fp32 MFMA (v_mfma_f32_16x16x4_f32), MI355X_MICROARCH.md"},
            "loss_last": float(loss)}
+    if kp_on:
+        # the keypoint kernel alone: B * Tp frames of one body, loss and accumulated gradient, as the step launches it
+        body = bodies[sorted(bodies)[0]]
+        P = ys[0].reshape(B * Tp, 66).contiguous()
+        K3, rb = kw[0]["target_keypoints"].reshape(B * Tp, 17, 3), kw[0]["betas"].repeat_interleave(Tp, 0).contiguous()
+        ol, og = torch.zeros(B * Tp, device="cuda"), torch.zeros((B * Tp, 66), device="cuda")
+        n = max(a.steps, 10)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for i in range(n + 3):
+            if i == 3:
+                ev[0].record()
+            body.keypoint_loss(P, K3, betas=rb, out_loss=ol, out_grad=og, grad_scale=1e-3, accumulate=True)
+        ev[1].record()
+        torch.cuda.synchronize()
+        parts = tr.last_loss_parts.cpu().numpy()
+        out["kp_loss"] = {"weight": a.kp_loss, "frames": B * Tp, "bodies": len(bodies),
+                          "kernel_ms": round(ev[0].elapsed_time(ev[1]) / n, 4),
+                          "kernel_scope": f"{n} back-to-back tik_fk_keypoint_loss launches of all frames on one body, HIP events",
+                          "pose_mse_last": float(parts[0]), "kp_mse_last": float(parts[1])}
     if a.eval:
         # the eval-mode pass on the live weights (tik_trainer_eval), same batches, same process
         batches = [{"keypoints_3d": xs[i], "poses": ys[i]} for i in range(4)]

@@ -315,6 +315,47 @@ int tik_trainer_set_steps(tik_trainer_t t, long long steps);
  * backward intermediates (10..14); n floats to device dst. Both variables
  * are read by tik_trainer_create, which refuses a layer outside 0..L-1. */
 int tik_trainer_debug(tik_trainer_t t, int which, int layer, float* dst, long long n, void* stream);
+/* The head of the last step (any layer index in range): which 7 its train-mode
+ * output (the predicted poses), 8 the loss gradient with respect to it, each
+ * as (N T', pose_dim) dense; whole rows only, min(n / pose_dim, N T') of them. */
+
+/* The training step with a keypoint term in the loss (tik_fk_keypoint_loss
+ * below, back-propagated through FK), pose_dim 66. With R = N T' rows,
+ *   kp_mse = (1 / (51 R)) sum_f sum_k w_k |r_fk|^2      (nn.MSELoss's normalisation of the 51 R residuals)
+ *   loss   = pose_mse + weight kp_mse
+ *   d loss / d poses[f] += weight (2 / (51 R)) J_f^T W r_f
+ * After the MSE gradient is written, one tik_fk_keypoint_loss launch per body
+ * model on its rows of the predicted poses (accumulate onto the gradient), then
+ * one reduction of the per-frame losses (fixed order, in double); the head and
+ * backbone backward and Adam follow unchanged. Rows that no list names count
+ * as zero. rows[i]: device int32, distinct rows of the (R, .) pose matrix for
+ * fk[i], n_rows[i] of them (0: no launch); no entry is range-checked on the
+ * device, and a row in two lists is the caller's error. rows[0] == NULL with
+ * n_models == 1: all R rows. kps (R,17,3), betas (R,nb) rows betas_ld apart
+ * (betas_ld 0: one row for all) or NULL, joint_w 17 shared weights or NULL: device
+ * fp32. loss: the total (device float, or NULL); loss_parts: {pose_mse, kp_mse}
+ * (two device floats, or NULL). kp == NULL: exactly the launches of
+ * tik_trainer_step (loss_parts must be NULL). weight == 0: kp_mse is still
+ * reported (a monitor), and every gradient, Adam moment and parameter has the
+ * bits of tik_trainer_step.
+ * TIK_E_INVALID, before any kernel touches running statistics: what
+ * tik_trainer_step refuses; a pose_dim other than 66; n_models outside 1..3; a
+ * null fk[i]; a null rows[i] except the all-rows case; a negative n_rows[i] or
+ * more than R rows in all; a null kps; a negative, NaN or infinite weight; what
+ * tik_fk_keypoint_loss refuses of a model or of betas_ld. */
+typedef struct {
+    int n_models;              /* 1..3 body models (genders) in this batch */
+    tik_fk_t fk[3];
+    const int* rows[3];
+    int n_rows[3];
+    const float* kps;
+    const float* betas;
+    int betas_ld;
+    const float* joint_w;
+    float weight;              /* >= 0 */
+} tik_kp_loss;
+int tik_trainer_step_kp(tik_trainer_t t, const float* x, int N, int T, const float* target, const float* dropout_mask,
+                        unsigned long long seed, const tik_kp_loss* kp, float* loss, float* loss_parts, void* stream);
 
 /* ------------------------------------------------------------------------
  * SMPL-X forward kinematics + linear blend skinning (the FK check).
@@ -561,6 +602,41 @@ int tik_fk_refine(tik_fk_t fk, const float* poses, const float* prior, const flo
                   const float* betas, int betas_ld, const float* joint_w, int joint_w_ld, const int* sel17, int iters,
                   float mu, float smooth, float lam0, int B, float* out_poses, float* out_cost, float* dbg_jac,
                   float* dbg_r, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The keypoint loss of a pose and its gradient with respect to the pose in
+ * one launch (the keypoint term of a training loss: HMR / VIBE style
+ * |rel(FK(pred)) - rel(kps)|^2, back-propagated through FK): one workgroup per
+ * frame, FK, residual and the analytic Jacobian in LDS (tik_fk_refine's device
+ * code, one FK state, no normal equations). Per frame f, theta the 66 pose
+ * values of joints 0..21 (the other joints stay at pose_mean):
+ *   r          = rel(FK keypoints(theta_f, betas_f)) - rel(kps_f)    rel(x) = x - mean of columns 11 and 12
+ *   loss[f]    = 1/2 sum_k w_k |r_k|^2                               (the data term of tik_fk_refine's cost)
+ *   g[q]       = sum_i w_i J[i][q] r[i]     i < 51, q < 66           (J^T W r, J with root-relative rows)
+ *   grad[f][q] = grad_scale g[q], or with accumulate != 0 fmaf(grad_scale, g[q], grad[f][q])
+ * poses: row f at poses + f poses_ld (poses_ld >= 66; the trainer's pose
+ * matrix has 68); kps (.,17,3); betas, betas_ld, joint_w, joint_w_ld, sel17
+ * exactly as in tik_fk_refine; loss indexed by frame, or NULL; grad: row f at
+ * grad + f grad_ld (grad_ld >= 66), or NULL; at least one of the two. All
+ * device fp32 but sel17 (host). rows: device int32 with B entries, or NULL for
+ * frames 0 .. B-1: workgroup b works on frame f = rows[b] for every input and
+ * output, frames not listed are not touched, distinct entries are the
+ * caller's promise, and NO index derived from rows is range-checked on the
+ * device: an entry outside the caller's arrays reads and writes out of bounds.
+ * A NaN keypoint or pose gives that frame a NaN loss and a NaN gradient row
+ * and affects no other frame. fp32 FMAs in a fixed order, no atomics, one
+ * writer per output element: a frame's bits do not depend on B, on its place
+ * in the batch or on rows (they are not those of tik_fk_joints_jacobian).
+ * Both skinning table forms of the handle. No workspace, nothing uploaded,
+ * stream-ordered.
+ * TIK_E_INVALID, before any device work: null fk / poses / kps, loss and grad
+ * both NULL, B <= 0, poses_ld < 66, grad_ld < 66 with grad, a grad_scale that
+ * is not finite, betas_ld not 0 or >= nb, joint_w_ld not 0 or 17, a joint index
+ * out of range, a landmark of three vertices or a contour landmark in sel17.
+ * ---------------------------------------------------------------------- */
+int tik_fk_keypoint_loss(tik_fk_t fk, const float* poses, int poses_ld, const float* kps, const float* betas, int betas_ld,
+                         const float* joint_w, int joint_w_ld, const int* sel17, const int* rows, int B, float* loss,
+                         float* grad, int grad_ld, float grad_scale, int accumulate, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,13 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.POINTER(ctypes.c_float)
 
+
+class TikKpLoss(ctypes.Structure):
+    """tik_kp_loss (include/tik.h): the keypoint term of tik_trainer_step_kp."""
+    _fields_ = [("n_models", _I), ("fk", _P * 3), ("rows", _P * 3), ("n_rows", _I * 3), ("kps", _P), ("betas", _P),
+                ("betas_ld", _I), ("joint_w", _P), ("weight", ctypes.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/tik.h declares
 SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_last_error": (ctypes.c_char_p, ()),
@@ -84,6 +91,8 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_lm_solve_chain": (_I, (_P, _P, _P, _P, _P, _I, _P, _P, ctypes.c_float, ctypes.c_float, _I, _I, _I, _I, _P, _P, _P)),
     "tik_fk_refine": (_I, (_P, _P, _P, _P, _P, _P, _I, _P, _I, ctypes.POINTER(_I), _I, ctypes.c_float, ctypes.c_float,
                            ctypes.c_float, _I, _P, _P, _P, _P, _P)),
+    "tik_fk_keypoint_loss": (_I, (_P, _P, _I, _P, _P, _I, _P, _I, ctypes.POINTER(_I), _P, _I, _P, _P, _I, ctypes.c_float, _I,
+                                  _P)),
     "tik_fk_workspace_bytes": (ctypes.c_longlong, (_P,)),
     "tik_fk_profile": (_I, (_P, _I)),
     "tik_fk_profile_count": (_I, (_P,)),
@@ -92,6 +101,7 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_trainer_create": (_I, (ctypes.POINTER(TikTensor), _I, ctypes.c_float, ctypes.POINTER(_P))),
     "tik_trainer_destroy": (_I, (_P,)),
     "tik_trainer_step": (_I, (_P, _P, _I, _I, _P, _P, ctypes.c_ulonglong, _P, _P)),
+    "tik_trainer_step_kp": (_I, (_P, _P, _I, _I, _P, _P, ctypes.c_ulonglong, ctypes.POINTER(TikKpLoss), _P, _P, _P)),
     "tik_trainer_out_frames": (_I, (_P, _I)),
     "tik_trainer_count": (_I, (_P,)),
     "tik_trainer_tensor": (_I, (_P, _I, ctypes.c_char_p, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_I),

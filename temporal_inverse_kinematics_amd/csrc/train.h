@@ -83,6 +83,12 @@ hipError_t launch_leaky_dropout_bwd(float* dP, const float* dD, const float* P, 
 // cols floats, dO rows of ldo (padding columns zeroed)
 hipError_t launch_mse(const float* O, int ldo, const float* T, long long rows, int cols, float* dO, float* loss,
                       hipStream_t st);
+// The keypoint term of the loss from the per-frame losses lf (rows; 1/2 sum_k w_k |r_k|^2 each, zero where no body
+// model has the row): kp_mse = 2 sum(lf) / (51 rows), summed in double in a fixed order as launch_mse sums.
+// loss[0] = pose_mse[0] + weight kp_mse (pose_mse[0] alone at weight 0; loss may be pose_mse);
+// parts (or null) = {pose_mse[0], kp_mse}
+hipError_t launch_kp_loss_reduce(const float* lf, long long rows, float weight, const float* pose_mse, float* loss,
+                                 float* parts, hipStream_t st);
 // Eval-mode BatchNorm folded into the forward GEMM operands (the host fold of
 // fold.h's fold_block, on the device, from the live parameters): per
 // channel sc = gamma / sqrt(running_var + eps) (the root in double), sh =

@@ -706,6 +706,35 @@ hipError_t launch_mse(const float* O, int ldo, const float* T, long long rows, i
     return hipGetLastError();
 }
 
+// one workgroup, mse_kernel's reduction: thread i adds rows i, i + 1024, .. in double, then the fixed tree
+__global__ __launch_bounds__(1024) void kp_loss_reduce_kernel(const float* __restrict__ lf, long long rows, float weight,
+                                                              const float* pose_mse, float* loss, float* parts) {
+    __shared__ double red[1024];
+    double s = 0.0;
+    for (long long i = threadIdx.x; i < rows; i += blockDim.x) s += (double)lf[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = blockDim.x / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float pm = pose_mse[0];
+        const float km = (float)(2.0 * red[0] / (51.0 * (double)rows));
+        if (parts) {
+            parts[0] = pm;
+            parts[1] = km;
+        }
+        loss[0] = weight > 0.f ? fmaf(weight, km, pm) : pm;
+    }
+}
+
+hipError_t launch_kp_loss_reduce(const float* lf, long long rows, float weight, const float* pose_mse, float* loss,
+                                 float* parts, hipStream_t st) {
+    hipLaunchKernelGGL(kp_loss_reduce_kernel, dim3(1), dim3(1024), 0, st, lf, rows, weight, pose_mse, loss, parts);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- eval pass
 // eval-mode BatchNorm of channel c as (scale, shift), the arithmetic of the
 // host fold (api.cpp bn_fold): the scale in double, both rounded to fp32 once

@@ -165,12 +165,23 @@ int tik_trainer_out_frames(tik_trainer_t t, int T) {
 // Debug / test hook on the last step's saved state: which = 0 block `layer`'s
 // output, 2 its tcn conv output U, 3 its ReLU(BN(mix)) H, 4 the mix output Z,
 // 5 the gcn conv output Y (channels-last rows), 6 the head's first Linear
-// output; 1 the block's input gradient and 10..14 its gS (identity-residual blocks),
+// output, 7 the head's train-mode output Oh and 8 its gradient dOh (both as
+// (N T', pose_dim) dense, whole rows only); 1 the block's input gradient and 10..14 its gS (identity-residual blocks),
 // dU, dH (before the ReLU backward, which is folded into the BatchNorm pass), dZ, dY
 // (recorded with TIK_TRAIN_DEBUG=1 / TIK_TRAIN_DEBUG_LAYER=l). Copies
 // min(n, size) floats to the device pointer dst.
 int tik_trainer_debug(tik_trainer_t t, int which, int layer, float* dst, long long n, void* stream) {
     if (!t || layer < 0 || layer >= (int)t->L.size() || !dst || n < 0) return fail(TIK_E_INVALID, "tik_trainer_debug: bad arguments");
+    if (which == 7 || which == 8) {   // the head's train-mode output Oh / its gradient dOh, rows of ldp -> (R, pose_dim) dense
+        const DevBuf& h = which == 7 ? t->Oh : t->dOh;
+        if (!h.p || t->N <= 0) return fail(TIK_E_INVALID, "tik_trainer_debug: buffer not recorded");
+        const size_t pd = (size_t)t->plan.pose_dim, R = (size_t)t->N * t->L.back().tout;
+        const size_t rows = std::min<size_t>((size_t)n / pd, R);
+        if (rows)
+            HIP_TRY(hipMemcpy2DAsync(dst, pd * sizeof(float), h.p, (size_t)t->plan.ldp * sizeof(float), pd * sizeof(float), rows,
+                                     hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return TIK_OK;
+    }
     const TrainLayer& l = t->L[layer];
     const DevBuf* b = which == 0 ? &l.O : which == 1 ? &t->dbg_dx[layer]
                     : which == 2 ? &l.U : which == 3 ? &l.H : which == 4 ? &l.Z : which == 5 ? &l.Y

@@ -31,6 +31,7 @@ struct tik_trainer {
     int N = 0, T = 0;
     std::vector<tik_train::Frames> fr;  // the frame chain of (N, T); sized once at create
     tik_host::DevBuf x4, x0, st0, k, Ph, Dh, Oh, dOh, dD, mask, loss, partf, gA, gB, tS, tU, tQ, tH, tZ, tY, col, up;
+    tik_host::DevBuf kpl;               // the per-frame keypoint losses of the last step (rows_h; tik_trainer_step_kp)
     tik_host::DevArray<double> partd;
     tik_host::DevIBuf cmap0;
     long long partf_cap = 0, partd_cap = 0;

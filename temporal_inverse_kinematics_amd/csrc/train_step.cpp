@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "fk_kploss.h"
 #include "train_model.h"
 
 using namespace tik_host;
@@ -90,7 +91,7 @@ int reserve(tik_trainer* t, int N, int T) {
         (rc = t->partd.reserve(t->partd_cap)) || (rc = t->gA.reserve(s.big)) || (rc = t->gB.reserve(s.big)) ||
         (rc = t->tS.reserve(s.big)) || (rc = t->tU.reserve(s.big)) || (rc = t->tQ.reserve(s.big)) ||
         (rc = t->tH.reserve(s.big)) || (rc = t->tZ.reserve(s.big)) || (rc = t->tY.reserve(s.big)) ||
-        (rc = t->col.reserve(s.colsz)) || (rc = t->up.reserve(s.big)))
+        (rc = t->col.reserve(s.colsz)) || (rc = t->up.reserve(s.big)) || (rc = t->kpl.reserve(s.rows_h)))
         return rc;
     // the gradient ping-pong buffers start zeroed (stream-ordered, in step()); their
     // padding column (layer 0's 4th input channel) is never read: bn_bwd_finalize
@@ -277,8 +278,35 @@ int backward_block(tik_trainer* t, int li, const float* X, int ldx, const float*
     return TIK_OK;
 }
 
+// The keypoint term of a step: one checked launch per body model (poses and grad still unset) and the weight.
+struct KpTerm {
+    int n = 0;
+    tik::FkKpLossArgs a[3];
+    float weight = 0.f;
+    float* parts = nullptr;   // {pose_mse, kp_mse} on the device, or null
+};
+
+// After launch_mse wrote dOh: every model's launch on its rows of Oh (the gradient onto dOh unless the weight is
+// 0), then loss_out = pose_mse + weight kp_mse.
+int kp_term(tik_trainer* t, KpTerm& kp, long long rows, float* loss_out, hipStream_t st) {
+    const int ldp = t->plan.ldp;
+    HIP_TRY(hipMemsetAsync(t->kpl.p, 0, rows * sizeof(float), st));   // rows that no list names count as zero
+    for (int i = 0; i < kp.n; ++i) {
+        tik::FkKpLossArgs& a = kp.a[i];
+        if (a.B == 0) continue;
+        a.poses = t->Oh.p; a.poses_ld = ldp;
+        a.loss = t->kpl.p;
+        a.grad = kp.weight > 0.f ? t->dOh.p : nullptr; a.grad_ld = ldp;
+        a.grad_scale = kp.weight * (2.f / (51.f * (float)rows));
+        a.accumulate = 1;
+        if (const int rc = tik::fk_kploss_launch(a, st)) return rc;
+    }
+    HIP_TRY(tik::launch_kp_loss_reduce(t->kpl.p, rows, kp.weight, loss_out, loss_out, kp.parts, st));
+    return TIK_OK;
+}
+
 int step(tik_trainer* t, const float* x, int N, int T, const float* target, const float* user_mask,
-         unsigned long long seed, float* loss_out, hipStream_t st) {
+         unsigned long long seed, float* loss_out, hipStream_t st, KpTerm* kp = nullptr) {
     const TrainPlan& p = t->plan;
     int rc;
     if ((rc = reserve(t, N, T))) return rc;
@@ -328,6 +356,7 @@ int step(tik_trainer* t, const float* x, int N, int T, const float* target, cons
         return rc;
     // MSE loss (PoseLosses, pose_trainer.py:42-50) and its gradient
     HIP_TRY(tik::launch_mse(t->Oh.p, p.ldp, target, rows, p.pose_dim, t->dOh.p, loss_out, st));
+    if (kp && (rc = kp_term(t, *kp, rows, loss_out, st))) return rc;
     // head backward
     if ((rc = colsum(t, t->dOh.p, rows, p.ldp, t->tS.p, st))) return rc;
     HIP_TRY(hipMemcpyAsync(Gd + p.b2, t->tS.p, p.pose_dim * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -373,4 +402,47 @@ extern "C" int tik_trainer_step(tik_trainer_t t, const float* x, int N, int T, c
         return fail(TIK_E_INVALID, "tik_trainer_step: batch of %d x %d frames too large", N, T);
     if (N * T < 2) return fail(TIK_E_INVALID, "tik_trainer_step: BatchNorm needs more than one value per channel");
     return step(t, x, N, T, target, dropout_mask, seed, loss ? loss : t->loss.p, (hipStream_t)stream);
+}
+
+extern "C" int tik_trainer_step_kp(tik_trainer_t t, const float* x, int N, int T, const float* target,
+                                   const float* dropout_mask, unsigned long long seed, const tik_kp_loss* kp, float* loss,
+                                   float* loss_parts, void* stream) {
+    const char* who = "tik_trainer_step_kp";
+    if (!t || !x || !target || N <= 0 || T <= 0) return fail(TIK_E_INVALID, "%s: bad arguments", who);
+    if (!batch_fits_32bit(t->plan, N, T)) return fail(TIK_E_INVALID, "%s: batch of %d x %d frames too large", who, N, T);
+    if (N * T < 2) return fail(TIK_E_INVALID, "%s: BatchNorm needs more than one value per channel", who);
+    float* lo = loss ? loss : t->loss.p;
+    if (!kp) {   // exactly the launches of tik_trainer_step
+        if (loss_parts) return fail(TIK_E_INVALID, "%s: loss_parts needs a keypoint term", who);
+        return step(t, x, N, T, target, dropout_mask, seed, lo, (hipStream_t)stream);
+    }
+    // every refusal before any kernel updates running statistics
+    if (t->plan.pose_dim != tik::LMR_N)
+        return fail(TIK_E_INVALID, "%s: the keypoint term needs pose_dim %d, the model has %d", who, tik::LMR_N, t->plan.pose_dim);
+    if (kp->n_models < 1 || kp->n_models > 3) return fail(TIK_E_INVALID, "%s: n_models must be 1..3, got %d", who, kp->n_models);
+    if (!kp->kps) return fail(TIK_E_INVALID, "%s: null kps", who);
+    if (!(kp->weight >= 0.f) || !std::isfinite(kp->weight))
+        return fail(TIK_E_INVALID, "%s: weight must be >= 0 and finite, got %g", who, (double)kp->weight);
+    const long long R = (long long)N * frame_chain(t->plan, T, nullptr);
+    KpTerm term;
+    term.n = kp->n_models;
+    term.weight = kp->weight;
+    term.parts = loss_parts;
+    long long named = 0;
+    for (int i = 0; i < kp->n_models; ++i) {
+        if (!kp->fk[i]) return fail(TIK_E_INVALID, "%s: fk[%d] is null", who, i);
+        const bool all = kp->n_models == 1 && !kp->rows[0];
+        if (!all && !kp->rows[i]) return fail(TIK_E_INVALID, "%s: rows[%d] is null", who, i);
+        const long long n = all ? R : kp->n_rows[i];
+        if (n < 0) return fail(TIK_E_INVALID, "%s: n_rows[%d] must be >= 0, got %lld", who, i, n);
+        named += n;
+        if (named > R) return fail(TIK_E_INVALID, "%s: the row lists name %lld rows, the batch has %lld", who, named, R);
+        // poses, loss and grad are the trainer's own buffers, set at the launch; kps stands in for them in the check
+        float* own = const_cast<float*>(kp->kps);
+        if (const int rc = tik::fk_kploss_args(kp->fk[i], who, own, t->plan.ldp, kp->kps, kp->betas, kp->betas_ld, kp->joint_w, 0,
+                                               nullptr, kp->rows[i], n > 0 ? (int)n : 1, own, nullptr, t->plan.ldp, 0.f, 1, term.a[i]))
+            return rc;
+        term.a[i].B = (int)n;
+    }
+    return step(t, x, N, T, target, dropout_mask, seed, lo, (hipStream_t)stream, &term);
 }

@@ -284,6 +284,43 @@ def _check_refine_tensors(num_betas, poses, kps, betas, prior, prev, joint_weigh
             REFINE_KPS if joint_weight is not None and joint_weight.dim() == 2 else 0)
 
 
+def _check_rows66(name, t, B):
+    """A float32 (B,66) tensor whose rows may be strided (stride(1) == 1, stride(0) >= 66) -> its leading dimension."""
+    if t.dim() != 2 or tuple(t.shape) != (B, REFINE_DOF):
+        raise ValueError(f"{name} must be {(B, REFINE_DOF)}, got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    if t.stride(1) != 1 or (B > 1 and t.stride(0) < REFINE_DOF):
+        raise ValueError(f"{name} must have unit stride along its rows and a row stride >= {REFINE_DOF}, got {t.stride()}")
+    return int(t.stride(0)) if B > 1 else max(int(t.stride(0)), REFINE_DOF)
+
+
+def check_kp_loss_tensors(num_betas, poses, kps, betas, joint_weight, rows, out_loss, out_grad, grad_scale):
+    """Shapes, dtypes and strides of SMPLX.keypoint_loss's tensors -> (B, poses_ld, betas_ld, joint_w_ld).
+    ValueError otherwise; neither the library nor the device is touched."""
+    if poses.dim() != 2 or poses.shape[0] < 1:
+        raise ValueError(f"poses must be (B >= 1, {REFINE_DOF}), got {tuple(poses.shape)}")
+    B = int(poses.shape[0])
+    poses_ld = _check_rows66("poses", poses, B)
+    if tuple(kps.shape) != (B, REFINE_KPS, 3):
+        raise ValueError(f"kps must be {(B, REFINE_KPS, 3)}, got {tuple(kps.shape)}")
+    if betas is not None and tuple(betas.shape) not in ((num_betas,), (B, num_betas)):
+        raise ValueError(f"betas must be {(num_betas,)} or {(B, num_betas)}, got {tuple(betas.shape)}")
+    if joint_weight is not None and tuple(joint_weight.shape) not in ((REFINE_KPS,), (B, REFINE_KPS)):
+        raise ValueError(f"joint_weight must be {(REFINE_KPS,)} or {(B, REFINE_KPS)}, got {tuple(joint_weight.shape)}")
+    _check_f32(kps=kps, betas=betas, joint_weight=joint_weight, out_loss=out_loss)
+    if out_loss is not None and tuple(out_loss.shape) != (B,):
+        raise ValueError(f"out_loss must be {(B,)}, got {tuple(out_loss.shape)}")
+    if out_grad is not None:
+        _check_rows66("out_grad", out_grad, B)
+    if rows is not None and (rows.dim() != 1 or rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() > B):
+        raise ValueError(f"rows must be a contiguous int32 (n <= {B},) tensor, got {rows.dtype} {tuple(rows.shape)}")
+    if not np.isfinite(float(grad_scale)):
+        raise ValueError(f"grad_scale must be finite, got {grad_scale}")
+    return (B, poses_ld, num_betas if betas is not None and betas.dim() == 2 else 0,
+            REFINE_KPS if joint_weight is not None and joint_weight.dim() == 2 else 0)
+
+
 def lm_chain_starts(F: int, seq_starts=None) -> np.ndarray:
     """The sequence boundaries lm_solve_chain takes: int32 (S+1,), sequence q the
     frames seq_starts[q] .. seq_starts[q+1] - 1. None: one sequence, [0, F].
@@ -573,6 +610,71 @@ class SMPLX:
                                              lam0, B, out.data_ptr(), cost.data_ptr(), _lib.ptr(jac), _lib.ptr(r),
                                              _lib.stream_of(poses)), "SMPLX.refine_frames")
         return (out, cost, jac, r) if debug else (out, cost)
+
+    def keypoint_loss(self, poses: torch.Tensor, kps: torch.Tensor, betas=None, joint_weight=None, rows=None, sel17=None,
+                      out_loss=None, out_grad=None, grad_scale: float = 1.0, accumulate: bool = False):
+        """The keypoint loss of B poses and its gradient with respect to them in one
+        launch (tik_fk_keypoint_loss, one workgroup per frame): poses (B,66), kps
+        (B,17,3) -> (loss (B,), grad (B,66)),
+        loss[f] = 1/2 sum_k w_k |r_k|^2, r = rel(FK keypoints(poses[f])) - rel(kps[f]),
+        grad[f] = grad_scale J^T W r (added to out_grad's rows with accumulate).
+        betas (nb,) or (B,nb) or None (the mean shape), joint_weight (17,) or (B,17)
+        non-negative or None (ones); poses and out_grad may be row-strided views
+        (stride(0) >= 66, stride(1) == 1), everything else contiguous float32 on the
+        device. sel17: "coco" (None) or 17 joint indices as in refine_frames. rows:
+        int32 (n,) device tensor of distinct frame indices in [0, B): only those
+        frames are read and written (out_loss / out_grad keep the others); the
+        range and distinctness are checked here, on the host copy, never on the
+        device. A NaN keypoint or pose gives that frame NaN and touches no other. A
+        frame's bits do not depend on B, on its place in the batch or on rows.
+        ValueError before the device is touched: a wrong shape, dtype or stride, a
+        grad_scale that is not finite, a landmark of three vertices in sel17."""
+        sel = resolve_refine_select("coco" if sel17 is None else sel17, self.num_joints)
+        B, poses_ld, betas_ld, jw_ld = check_kp_loss_tensors(self.num_betas, poses, kps, betas, joint_weight, rows,
+                                                              out_loss, out_grad, grad_scale)
+        _lib.require_gpu(kps, betas, joint_weight, out_loss)
+        for t in (poses, out_grad, rows):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("temporal_inverse_kinematics_amd ops run on the GPU only (got a CPU tensor)")
+        dev = poses.device
+        n = B
+        if rows is not None:
+            n = int(rows.numel())
+            rh = rows.detach().cpu().numpy()
+            if n and (rh.min() < 0 or rh.max() >= B or len(np.unique(rh)) != n):
+                raise ValueError(f"rows must be distinct frame indices in [0, {B})")
+        loss = out_loss if out_loss is not None else torch.zeros((B,), device=dev, dtype=torch.float32)
+        grad = out_grad if out_grad is not None else torch.zeros((B, REFINE_DOF), device=dev, dtype=torch.float32)
+        if n == 0:
+            return loss, grad
+        csel = (_lib.ctypes.c_int * REFINE_KPS)(*sel)
+        _lib.check(_lib.load().tik_fk_keypoint_loss(self._h, poses.data_ptr(), poses_ld, kps.data_ptr(), _lib.ptr(betas), betas_ld,
+                                                    _lib.ptr(joint_weight), jw_ld, csel, _lib.ptr(rows), n, loss.data_ptr(),
+                                                    grad.data_ptr(), max(int(grad.stride(0)), REFINE_DOF), float(grad_scale), int(bool(accumulate)),
+                                                    _lib.stream_of(poses)), "SMPLX.keypoint_loss")
+        return loss, grad
+
+    def keypoint_loss_fn(self, kps: torch.Tensor, betas=None, joint_weight=None):
+        """-> fn(poses (B,66)) = the per-frame keypoint loss (B,) of keypoint_loss,
+        differentiable with respect to poses only (a torch.autograd.Function:
+        backward multiplies the kernel's gradient rows by the incoming (B,)
+        gradient). A torch model's pose head trains on it with
+        fn(pred).mean().backward()."""
+        model = self
+
+        class _KeypointLoss(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, poses):
+                loss, grad = model.keypoint_loss(poses.detach().contiguous(), kps, betas, joint_weight)
+                ctx.save_for_backward(grad)
+                return loss
+
+            @staticmethod
+            def backward(ctx, dloss):
+                (grad,) = ctx.saved_tensors
+                return grad * dloss.unsqueeze(1)
+
+        return _KeypointLoss.apply
 
     @property
     def workspace_bytes(self) -> int:

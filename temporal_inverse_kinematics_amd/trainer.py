@@ -45,6 +45,56 @@ from .models import IKPoseTrainer, PoseRegressor, _Handle, _state_numpy
 
 _WHAT = {"value": 0, "grad": 1, "exp_avg": 2, "exp_avg_sq": 3}
 _CKPT_NAME = re.compile(r"^checkpoint_epoch=(\d+)-val_loss=(-?\d+\.\d\d|nan|inf)\.ckpt$")
+KP_POSE_DIM, KP_JOINTS = 66, 17   # include/tik.h, tik_trainer_step_kp
+
+
+def check_kp_args(kp_weight, n_models: int, pose_dim: int = KP_POSE_DIM, N=None, To=None, num_betas=None,
+                  target_keypoints=None, betas=None, gender_id=None, kp_joint_weight=None) -> float:
+    """The keypoint term's arguments of GpuTrainer, constructor and step alike -> kp_weight as a float.
+    A pure function of shapes and host values: neither the library nor the device is touched.
+    n_models: body models given (0: none). With N and To (the step's batch): target_keypoints must be
+    (N,To,17,3), betas None, (nb,), (N,nb) or (N,To,nb), gender_id None (one model only) or N integers in [0, n_models)
+    (a host sequence or array). ValueError: kp_weight negative or NaN; kp_weight > 0 without body models; with
+    body models a pose_dim other than 66, a wrong shape, an unknown gender index, kp_joint_weight not (17,)."""
+    w = float(kp_weight)
+    if not w >= 0.0 or w == float("inf"):
+        raise ValueError(f"kp_weight must be >= 0 and finite, got {kp_weight}")
+    if n_models == 0:
+        if w > 0.0:
+            raise ValueError("kp_weight > 0 needs smplx_models: the keypoint term runs FK on the predicted poses")
+        return w
+    if not 1 <= n_models <= 3:
+        raise ValueError(f"the keypoint term takes 1..3 body models, got {n_models}")
+    if int(pose_dim) != KP_POSE_DIM:
+        raise ValueError(f"the keypoint term needs pose_dim {KP_POSE_DIM} (22 joints x 3), the model has {pose_dim}")
+    if kp_joint_weight is not None and tuple(np.shape(kp_joint_weight)) != (KP_JOINTS,):
+        raise ValueError(f"kp_joint_weight must be ({KP_JOINTS},), got {tuple(np.shape(kp_joint_weight))}")
+    if N is None:
+        return w
+    if target_keypoints is None or tuple(target_keypoints.shape) != (N, To, KP_JOINTS, 3):
+        got = None if target_keypoints is None else tuple(target_keypoints.shape)
+        raise ValueError(f"target_keypoints must be {(N, To, KP_JOINTS, 3)}, got {got}")
+    if betas is not None and tuple(betas.shape) not in ((num_betas,), (N, num_betas), (N, To, num_betas)):
+        raise ValueError(f"betas must be {(num_betas,)}, {(N, num_betas)} or {(N, To, num_betas)}, got {tuple(betas.shape)}")
+    if gender_id is None:
+        if n_models != 1:
+            raise ValueError(f"gender_id is required with {n_models} body models")
+        return w
+    g = np.asarray(gender_id)
+    if g.shape != (N,) or g.dtype.kind not in "iu":
+        raise ValueError(f"gender_id must be {(N,)} integers, got {g.dtype} {g.shape}")
+    if N and (g.min() < 0 or g.max() >= n_models):
+        raise ValueError(f"gender_id holds an index outside [0, {n_models}): the body models are sorted(smplx_models)")
+    return w
+
+
+def _rows_betas(b: torch.Tensor, To: int) -> torch.Tensor:
+    """betas (nb,), (N,nb) or (N,T',nb) -> one shared row (nb,) or one row per pose row (N T', nb), contiguous."""
+    if b.dim() == 2:
+        b = b.repeat_interleave(To, 0)
+    elif b.dim() == 3:
+        b = b.reshape(-1, b.shape[2])
+    return b.contiguous()
 
 
 class GpuTrainer:
@@ -55,10 +105,22 @@ class GpuTrainer:
     >>> out["loss"], out["log"]["train/pose_mse"]
     """
 
-    def __init__(self, model, lr: Optional[float] = None, device="cuda"):
+    def __init__(self, model, lr: Optional[float] = None, device="cuda", smplx_models=None, kp_weight: float = 0.0,
+                 kp_joint_weight=None):
+        """smplx_models ({gender: SMPLX}, at most 3) switches the keypoint term on: the step
+        becomes tik_trainer_step_kp, loss = pose_mse + kp_weight * kp_mse with kp_mse the
+        nn.MSELoss of rel(FK(predicted poses)) against rel(batch["target_keypoints_3d"]),
+        back-propagated through FK. kp_weight = 0 only monitors kp_mse (the update keeps the
+        bits of the plain step). kp_joint_weight: 17 non-negative keypoint weights or None."""
         reg = model.regressor if isinstance(model, IKPoseTrainer) else model
         if not isinstance(reg, PoseRegressor):
             raise TypeError("GpuTrainer expects an IKPoseTrainer or PoseRegressor")
+        self.smplx_models = dict(smplx_models) if smplx_models else None
+        self._genders = sorted(self.smplx_models) if self.smplx_models else []
+        self.kp_weight = check_kp_args(kp_weight, len(self._genders), reg.pose_dim, kp_joint_weight=kp_joint_weight)
+        self._kp_jw = None
+        if kp_joint_weight is not None and self.smplx_models:
+            self._kp_jw = torch.as_tensor(np.asarray(kp_joint_weight, np.float32)).to(device).contiguous()
         hp = getattr(model, "hparams", None)
         if lr is None:
             lr = float(getattr(hp, "lr", 1e-4)) if hp is not None else 1e-4
@@ -82,15 +144,21 @@ class GpuTrainer:
             self._names.append((name.value.decode(), tuple(shape[:nd.value]), kind.value))
         self._index = {n: i for i, (n, _, _) in enumerate(self._names)}
         self._loss = torch.zeros(1, device=self.device)
+        self._parts = torch.zeros(2, device=self.device)   # {pose_mse, kp_mse} of the last keypoint step
         # the BatchNorm step counters the model arrived with (checkpoint / earlier training)
         self._nbt0 = {k: int(v.item()) for k, v in reg.state_dict().items() if k.endswith("num_batches_tracked")}
 
     # ------------------------------------------------------------------ step
     def step(self, keypoints_3d: torch.Tensor, poses: torch.Tensor, dropout_mask: Optional[torch.Tensor] = None,
-             seed: int = 0) -> torch.Tensor:
+             seed: int = 0, target_keypoints=None, betas=None, gender_id=None) -> torch.Tensor:
         """One optimizer step on (keypoints_3d (N,T,17,3), poses (N,T',66)); returns the
         pre-update loss as a device scalar. `dropout_mask` (N*T', 512) of 0/1 fixes the
-        head's dropout draw (tests); otherwise a counter-based mask keyed by `seed`."""
+        head's dropout draw (tests); otherwise a counter-based mask keyed by `seed`.
+        With smplx_models (tik_trainer_step_kp): target_keypoints (N,T',17,3) the clean
+        keypoints of the target poses (not root-relative: the kernel applies rel), betas
+        None, (nb,), (N,nb) (a window's betas serve its T' rows) or (N,T',nb), gender_id (N,) integers
+        indexing sorted(smplx_models) (None with one model); the loss returned is
+        pose_mse + kp_weight * kp_mse and `last_loss_parts` holds the two terms."""
         x = keypoints_3d.contiguous()
         y = poses.contiguous()
         _lib.require_gpu(x, y)
@@ -109,17 +177,72 @@ class GpuTrainer:
             if dropout_mask.numel() != N * To * 512:
                 raise ValueError("dropout_mask must hold N*T'*512 values")
             mptr = dropout_mask.data_ptr()
+        if self.smplx_models:
+            self._step_kp(lib, x, y, N, T, To, mptr, int(seed) & (2**64 - 1), target_keypoints, betas, gender_id)
+            return self._loss[0].clone()
         _lib.check(lib.tik_trainer_step(self._h.h, x.data_ptr(), N, T, y.data_ptr(), mptr, int(seed) & (2**64 - 1),
                                         self._loss.data_ptr(), _lib.stream_of(x)), "GpuTrainer.step")
         # a fresh tensor per step (the reference returns a new loss each step;
         # the persistent device buffer is overwritten by the next step)
         return self._loss[0].clone()
 
+    def _step_kp(self, lib, x, y, N, T, To, mptr, seed, target_keypoints, betas, gender_id):
+        """The tik_trainer_step_kp call: every check on the host first, the per-model row lists built on the device."""
+        models = [self.smplx_models[g] for g in self._genders]
+        nb = models[0].num_betas
+        gid_host = None
+        if gender_id is not None:
+            gid_host = gender_id.detach().cpu().numpy() if isinstance(gender_id, torch.Tensor) else np.asarray(gender_id)
+        check_kp_args(self.kp_weight, len(models), self.regressor.pose_dim, N, To, nb, target_keypoints, betas, gid_host)
+        kps = target_keypoints.to(self.device, torch.float32).contiguous()
+        R = N * To
+        kp = _lib.TikKpLoss()
+        kp.n_models = len(models)
+        keep = [kps]
+        if gid_host is None:
+            kp.fk[0], kp.rows[0], kp.n_rows[0] = models[0]._h, None, R
+        else:
+            # the row lists on the device, back to back in one tensor: a stable sort of the rows by model keeps each list
+            # ascending; the counts come from the host copy the check has read already (no further synchronisation)
+            gid = (gender_id if isinstance(gender_id, torch.Tensor) else torch.as_tensor(gid_host)).to(self.device)
+            rows = torch.argsort(gid.long().repeat_interleave(To), stable=True).to(torch.int32).contiguous()
+            keep.append(rows)
+            counts = np.bincount(gid_host.astype(np.int64), minlength=len(models)) * To
+            off = 0
+            for i, m in enumerate(models):
+                # an empty list still gets a non-null pointer: the all-rows case is the only null
+                kp.fk[i], kp.rows[i], kp.n_rows[i] = m._h, rows.data_ptr() + 4 * off, int(counts[i])
+                off += int(counts[i])
+        kp.kps = kps.data_ptr()
+        if betas is not None:
+            b = _rows_betas(betas.to(self.device, torch.float32), To)
+            keep.append(b)
+            kp.betas, kp.betas_ld = b.data_ptr(), (nb if b.dim() == 2 else 0)
+        kp.joint_w = _lib.ptr(self._kp_jw) or None
+        kp.weight = self.kp_weight
+        _lib.check(lib.tik_trainer_step_kp(self._h.h, x.data_ptr(), N, T, y.data_ptr(), mptr, seed, ctypes.byref(kp),
+                                           self._loss.data_ptr(), self._parts.data_ptr(), _lib.stream_of(x)),
+                   "GpuTrainer.step")
+        self._kp_keep = keep   # the step is stream-ordered: its inputs live until the next one replaces them
+
+    @property
+    def last_loss_parts(self) -> torch.Tensor:
+        """{pose_mse, kp_mse} of the last keypoint step, a fresh (2,) device tensor."""
+        return self._parts.clone()
+
     def training_step(self, batch: Dict[str, torch.Tensor], batch_idx: int = 0, dropout_mask=None):
-        """pose_trainer.py:146-155 plus Lightning's backward and optimizer step."""
-        loss = self.step(batch["keypoints_3d"].to(self.device), batch["poses"].to(self.device), dropout_mask,
-                         seed=self.steps * 1000003 + batch_idx)
-        return {"loss": loss, "log": {"train/pose_mse": loss}}
+        """pose_trainer.py:146-155 plus Lightning's backward and optimizer step. With
+        smplx_models the batch also carries target_keypoints_3d, betas and (more than one
+        model) gender_id, and the log has both terms of the loss."""
+        seed = self.steps * 1000003 + batch_idx
+        if not self.smplx_models:
+            loss = self.step(batch["keypoints_3d"].to(self.device), batch["poses"].to(self.device), dropout_mask, seed=seed)
+            return {"loss": loss, "log": {"train/pose_mse": loss}}
+        loss = self.step(batch["keypoints_3d"].to(self.device), batch["poses"].to(self.device), dropout_mask, seed=seed,
+                         target_keypoints=batch["target_keypoints_3d"], betas=batch.get("betas"),
+                         gender_id=batch.get("gender_id"))
+        parts = self.last_loss_parts
+        return {"loss": loss, "log": {"train/pose_mse": parts[0], "train/kp_mse": parts[1]}}
 
     # ------------------------------------------------------------------ state
     @property
@@ -145,13 +268,14 @@ class GpuTrainer:
     def grads(self) -> Dict[str, torch.Tensor]:
         return {n: self.tensor(n, "grad") for n, _, k in self._names if k == 0}
 
-    _SAVED = {"O": 0, "U": 2, "H": 3, "Z": 4, "Y": 5, "P": 6}
+    _SAVED = {"O": 0, "U": 2, "H": 3, "Z": 4, "Y": 5, "P": 6, "poses": 7, "dposes": 8}
 
     def saved(self, kind: str, layer: int, shape) -> torch.Tensor:
         """The last step's saved forward activation (test / debug hook): block `layer`'s
         output "O", tcn conv output "U", post-ReLU tcn input "H", graph-mix output "Z",
         gcn conv output "Y" (channels-last (N,T,17,C)); "P" the head's first Linear
-        output (N*T', 512)."""
+        output (N*T', 512); "poses" the head's train-mode output and "dposes" the loss
+        gradient with respect to it (layer 0, (N*T', 66))."""
         out = torch.empty(shape, device=self.device, dtype=torch.float32)
         _lib.check(_lib.load().tik_trainer_debug(self._h.h, self._SAVED[kind], layer, out.data_ptr(), out.numel(),
                                                  _lib.stream_of(out)), "saved")
@@ -208,12 +332,41 @@ class GpuTrainer:
 
     def validation_step(self, batch: Dict[str, torch.Tensor], batch_idx: int = 0):
         """pose_trainer.py:158-164; the loss is a fresh device scalar each call."""
-        _, lss = self.evaluate(batch["keypoints_3d"].to(self.device), batch["poses"].to(self.device), want_poses=False)
-        return {"val_loss": lss, "pose_mse": lss}
+        if not self.smplx_models:
+            _, lss = self.evaluate(batch["keypoints_3d"].to(self.device), batch["poses"].to(self.device), want_poses=False)
+            return {"val_loss": lss, "pose_mse": lss}
+        poses, lss = self.evaluate(batch["keypoints_3d"].to(self.device), batch["poses"].to(self.device))
+        kp = self.keypoint_mse(poses, batch["target_keypoints_3d"], batch.get("betas"), batch.get("gender_id"))
+        return {"val_loss": lss + self.kp_weight * kp, "pose_mse": lss, "kp_mse": kp}
+
+    def keypoint_mse(self, poses, target_keypoints, betas=None, gender_id=None) -> torch.Tensor:
+        """kp_mse of poses (N,T',66) against target_keypoints (N,T',17,3), the step's
+        normalisation 2 sum(loss) / (51 N T'), through SMPLX.keypoint_loss per body model."""
+        N, To = int(poses.shape[0]), int(poses.shape[1])
+        models = [self.smplx_models[g] for g in self._genders]
+        gid_host = None
+        if gender_id is not None:
+            gid_host = gender_id.detach().cpu().numpy() if isinstance(gender_id, torch.Tensor) else np.asarray(gender_id)
+        check_kp_args(self.kp_weight, len(models), poses.shape[2], N, To, models[0].num_betas, target_keypoints, betas, gid_host)
+        R = N * To
+        P = poses.reshape(R, KP_POSE_DIM).contiguous()
+        K = target_keypoints.to(self.device, torch.float32).reshape(R, KP_JOINTS, 3).contiguous()
+        b = None
+        if betas is not None:
+            b = _rows_betas(betas.to(self.device, torch.float32), To)
+        loss = torch.zeros(R, device=self.device)
+        grad = torch.empty((R, KP_POSE_DIM), device=self.device)
+        for i, m in enumerate(models):
+            rows = None
+            if gid_host is not None:
+                gid = torch.as_tensor(gid_host.astype(np.int64)).to(self.device).repeat_interleave(To)
+                rows = torch.nonzero(gid == i).flatten().to(torch.int32).contiguous()
+            m.keypoint_loss(P, K, betas=b, joint_weight=self._kp_jw, rows=rows, out_loss=loss, out_grad=grad)
+        return loss.double().sum().mul(2.0 / (51.0 * R)).float()
 
     def validation_epoch_end(self, outputs):
         """pose_trainer.py:166-172: the mean of the batch means."""
-        losses = calc_mean_losses(outputs, ["pose_mse", "val_loss"])
+        losses = calc_mean_losses(outputs, ["pose_mse", "kp_mse", "val_loss"])
         return {"val_loss": losses["val_loss"], "log": {f"val/{k}": v for k, v in losses.items()}}
 
     def validate(self, val_ds, batch_size: int):
@@ -253,7 +406,7 @@ class GpuTrainer:
         torch.save(ck, str(path))
         return str(path)
 
-    def _restore(self, path, device) -> dict:
+    def _restore(self, path, device, **kp_kwargs) -> dict:
         """Rebuild this trainer from a checkpoint: weights and running statistics
         (IKPoseTrainer.load_from_checkpoint), both Adam moments, steps and lr. A file
         without optimizer_states gives fresh Adam state and steps = 0.
@@ -267,7 +420,7 @@ class GpuTrainer:
         ck = torch.load(str(path), map_location="cpu", weights_only=True)
         opt = (ck.get("optimizer_states") or [None])[0]
         lr = float(opt["param_groups"][0]["lr"]) if opt else None
-        GpuTrainer.__init__(self, model, lr=lr, device=device)
+        GpuTrainer.__init__(self, model, lr=lr, device=device, **kp_kwargs)
         if opt:
             for i, n in enumerate(self._param_order()):
                 st = opt["state"].get(i)
@@ -282,10 +435,12 @@ class GpuTrainer:
         return ck
 
     @classmethod
-    def from_checkpoint(cls, path, device="cuda") -> "GpuTrainer":
-        """A trainer that continues where `save_checkpoint` stopped."""
+    def from_checkpoint(cls, path, device="cuda", smplx_models=None, kp_weight: float = 0.0,
+                        kp_joint_weight=None) -> "GpuTrainer":
+        """A trainer that continues where `save_checkpoint` stopped. The keypoint term's
+        arguments are the constructor's: the checkpoint does not store them."""
         tr = cls.__new__(cls)
-        tr._restore(path, device)
+        tr._restore(path, device, smplx_models=smplx_models, kp_weight=kp_weight, kp_joint_weight=kp_joint_weight)
         return tr
 
     # ------------------------------------------------------------------ fit
@@ -308,7 +463,8 @@ class GpuTrainer:
         start, kept = 0, []
         ckpt_dir = None if ckpt_dir is None else str(ckpt_dir)
         if resume_ckpt:
-            ck = self._restore(resume_ckpt, self.device)
+            ck = self._restore(resume_ckpt, self.device, smplx_models=self.smplx_models, kp_weight=self.kp_weight,
+                               kp_joint_weight=None if self._kp_jw is None else self._kp_jw.cpu().numpy())
             e = int(ck["epoch"])
             train_ds.on_epoch_end(e)
             start = e + 1
@@ -400,13 +556,23 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def build_train_parser() -> argparse.ArgumentParser:
+    """build_parser() plus this project's own training options, which the reference does not have."""
+    p = build_parser()
+    p.add_argument("--kp_weight", type=float, default=0.0,
+                   help="weight of the keypoint term rel(FK(pred)) vs rel(keypoints) in the loss (0: pose MSE alone)")
+    return p
+
+
 def run_train(argv=None) -> int:
     """pose_trainer.py:233-256: train.csv / valid.csv under --data_dir, SMPL-X models
     from <amass>/smplx, the shape DB <amass>/smplx_shapes.npz for the training set
     only, checkpoints (top 30) under <data_dir>/model_ckps/."""
     from .smplx_fk import load_smplx_models
     from .training_data import AmassDataset
-    hp = build_parser().parse_args(argv)
+    hp = build_train_parser().parse_args(argv)
+    kp_weight = hp.kp_weight
+    del hp.kp_weight                    # not a hyper-parameter of the model: the checkpoint's hparams keep their keys
     data_dir = Path(hp.data_dir)
     train_paths = _load_amass_path_list(data_dir / "train.csv")
     val_paths = _load_amass_path_list(data_dir / "valid.csv")
@@ -417,12 +583,13 @@ def run_train(argv=None) -> int:
     shape_path = Path(hp.amass) / "smplx_shapes.npz"
     if not shape_path.exists():
         raise FileNotFoundError(f"smplx_shapes.npz is not found under {hp.amass}")
+    kp_on = check_kp_args(kp_weight, 0 if kp_weight == 0 else 3) > 0.0
     smplx = load_smplx_models(None if hp.synthetic_smplx else Path(hp.amass) / "smplx", "cuda", batch_size=1024)
     train_ds = AmassDataset(smplx_models=smplx, amass_paths=train_paths, window_size=hp.win_size,
-                            keypoint_format=hp.keypoint_format, shape_db_path=shape_path)
+                            keypoint_format=hp.keypoint_format, shape_db_path=shape_path, target_keypoints=kp_on)
     val_ds = AmassDataset(smplx_models=smplx, amass_paths=val_paths, window_size=hp.win_size,
-                          keypoint_format=hp.keypoint_format)
-    tr = GpuTrainer(IKPoseTrainer(hp))
+                          keypoint_format=hp.keypoint_format, target_keypoints=kp_on)
+    tr = GpuTrainer(IKPoseTrainer(hp), **({"smplx_models": smplx, "kp_weight": kp_weight} if kp_on else {}))
     if hp.resume_ckpt:
         print(f"resume from checkpoint: {hp.resume_ckpt}")
     else:

@@ -89,11 +89,17 @@ class AmassDataset(torch.utils.data.Dataset):
     without building the bodies (SMPLX.joints). Each sequence's `keypoints_3d`
     is then (F, 17, 3), already in target (COCO) order, instead of the (F, 144,
     3) SMPL-X joints; items agree with the default's within the two FK paths'
-    difference (a few 1e-4 at most)."""
+    difference (a few 1e-4 at most).
+
+    target_keypoints=True: `get_batch` adds what the trainer's keypoint term reads:
+    "target_keypoints_3d" (B,1,17,3), the clean FK keypoints (no noise, not
+    root-relative) of the frame whose pose row is the target, and "gender_id"
+    (B,) int32, each item's body model as an index into sorted(smplx_models)."""
 
     def __init__(self, smplx_models, amass_paths: List, window_size: int, keypoint_format: str, device="cuda",
                  add_gaussian_noise=True, shape_db_path: Optional[Path] = None, aug_shape=True,
-                 aug_root_orientation=True, noise_seed: int = 0, mesh_free: bool = False):
+                 aug_root_orientation=True, noise_seed: int = 0, mesh_free: bool = False,
+                 target_keypoints: bool = False):
         self.origin_amass_paths = amass_paths
         self.device = torch.device(device)
         self.smplx_models = smplx_models
@@ -105,6 +111,7 @@ class AmassDataset(torch.utils.data.Dataset):
         self.aug_shape = aug_shape
         self.noise_seed = int(noise_seed)
         self.mesh_free = bool(mesh_free)
+        self.target_keypoints = bool(target_keypoints)
         self.epoch = 0
         self.smplx_shape_db = None
         if shape_db_path is not None:
@@ -176,7 +183,7 @@ class AmassDataset(torch.utils.data.Dataset):
             self._starts = np.zeros(0, np.int64)
             self._lens = np.zeros(0, np.int64)
             self._cum = np.zeros(0, np.int64)
-            self._betas = None
+            self._betas = self._gender = None
             return
         lens = np.array([int(d["poses"].shape[0]) for d in self.data_anims], np.int64)
         pw = max(66, max(int(d["poses"].shape[1]) for d in self.data_anims))
@@ -191,6 +198,8 @@ class AmassDataset(torch.utils.data.Dataset):
         self._lens = lens
         self._cum = np.cumsum(lens)
         self._betas = torch.from_numpy(np.stack([np.asarray(d["betas"], np.float32) for d in self.data_anims])).to(self.device)
+        order = {g: i for i, g in enumerate(sorted(self.smplx_models))}
+        self._gender = torch.tensor([order[str(d["gender"])] for d in self.data_anims], dtype=torch.int32, device=self.device)
 
     @property
     def noise_key(self) -> int:
@@ -221,7 +230,8 @@ class AmassDataset(torch.utils.data.Dataset):
         return seq, local, F
 
     def get_batch(self, indices) -> Dict[str, torch.Tensor]:
-        """Items `indices` at once: keypoints_3d (B, 2h+1, 17, 3), poses (B, 1, 66), betas (B, nb) on the device."""
+        """Items `indices` at once: keypoints_3d (B, 2h+1, 17, 3), poses (B, 1, 66), betas (B, nb) on the device;
+        with target_keypoints also target_keypoints_3d (B, 1, 17, 3) and gender_id (B,) int32."""
         idx = np.asarray(indices, np.int64).reshape(-1)
         seq, local, F = self._items(idx)
         B, W = idx.size, 2 * self.half_win_size + 1
@@ -241,9 +251,20 @@ class AmassDataset(torch.utils.data.Dataset):
                 "AmassDataset.get_batch")
         betas = (self._betas.index_select(0, meta[4].long()) if B
                  else torch.zeros((0, 10), device=self.device, dtype=torch.float32))
-        return {"keypoints_3d": win, "poses": tgt, "betas": betas}
+        out = {"keypoints_3d": win, "poses": tgt, "betas": betas}
+        if self.target_keypoints:
+            # the frame train_data.hip takes the target pose row from: the last frame of the edge-padded window
+            cols = None if self.mesh_free else torch.tensor(self.target_kps_mapping, device=self.device)
+            if B:
+                row = torch.from_numpy(self._starts[seq] + np.minimum(local + self.half_win_size, F - 1)).to(self.device)
+                kp = self._joints.index_select(0, row)
+                out["target_keypoints_3d"] = (kp if cols is None else kp.index_select(1, cols)).reshape(B, 1, 17, 3).contiguous()
+                out["gender_id"] = self._gender.index_select(0, meta[4].long())
+            else:
+                out["target_keypoints_3d"] = torch.zeros((0, 1, 17, 3), device=self.device, dtype=torch.float32)
+                out["gender_id"] = torch.zeros((0,), device=self.device, dtype=torch.int32)
+        return out
 
     def __getitem__(self, idx):
         b = self.get_batch([idx])
-        return {"keypoints_3d": b["keypoints_3d"][0].cpu().numpy(), "poses": b["poses"][0].cpu().numpy(),
-                "betas": b["betas"][0].cpu().numpy()}
+        return {k: v[0].cpu().numpy() for k, v in b.items()}
