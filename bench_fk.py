@@ -1,7 +1,7 @@
 """Config #4: SMPL-X full 55-joint FK + 10475-vertex LBS, batch=4096, 1 GPU.
 
     python bench_fk.py [--batch 4096] [--steps 10] [--warmup 20] [--joints {all,coco}] [--jacobian] [--refine] [--refine-fused]
-                       [--shape-jacobian] [--fit-shape] [--smooth]
+                       [--robust S] [--shape-jacobian] [--fit-shape] [--smooth]
 
 Prints one JSON line: bodies/s, and per kernel (HIP events around every launch
 of a second pass of the same steps, tik_fk_profile) the algorithmic TFLOP/s of
@@ -243,10 +243,11 @@ def measure_refine(batch=4096, steps=10, warmup=20):
                      "host-to-device uploads and the copy back; lm_solve: (batch,51,66) systems, output allocated per call"}
 
 
-def measure_refine_fused(batch=4096, steps=10, warmup=20, iters=3):
+def measure_refine_fused(batch=4096, steps=10, warmup=20, iters=3, robust=0.0):
     """The fused path beside measure_refine, same frames: refine_poses(fused=True) at `iters` and at 0 iterations
     (uploads, the first cost and the copies back are in both), their difference per iteration; and
-    SMPLX.refine_frames alone on resident tensors, per iteration."""
+    SMPLX.refine_frames alone on resident tensors, per iteration. robust > 0: the Geman-McClure data term at that
+    scale (metres) in all four."""
     import numpy as np
     import torch
     from temporal_inverse_kinematics_amd import _build, synthetic as syn
@@ -260,12 +261,12 @@ def measure_refine_fused(batch=4096, steps=10, warmup=20, iters=3):
     full[:, :22] = torch.from_numpy(pose[:, :22]).cuda() + 0.05
     kps_d = m.joints(full, select="coco")
     kps = kps_d.cpu().numpy()
-    tn, rn = _timed(lambda: refine_poses(th0, kps, m, iters=iters, fused=True), steps, warmup)
-    t0, r0 = _timed(lambda: refine_poses(th0, kps, m, iters=0, fused=True), steps, warmup)
+    tn, rn = _timed(lambda: refine_poses(th0, kps, m, iters=iters, fused=True, robust_sigma=robust), steps, warmup)
+    t0, r0 = _timed(lambda: refine_poses(th0, kps, m, iters=0, fused=True, robust_sigma=robust), steps, warmup)
     th_d = torch.from_numpy(th0).cuda()
-    kn, krn = _timed(lambda: m.refine_frames(th_d, kps_d, iters=iters), steps, warmup)
-    k0, kr0 = _timed(lambda: m.refine_frames(th_d, kps_d, iters=0), steps, warmup)
-    return {"batch": batch, "steps": steps, "warmup": warmup, "iters": iters,
+    kn, krn = _timed(lambda: m.refine_frames(th_d, kps_d, iters=iters, robust_sigma=robust), steps, warmup)
+    k0, kr0 = _timed(lambda: m.refine_frames(th_d, kps_d, iters=0, robust_sigma=robust), steps, warmup)
+    return {"batch": batch, "steps": steps, "warmup": warmup, "iters": iters, **({"robust_sigma": robust} if robust else {}),
             "lm_iteration_ms": round((tn - t0) / iters, 4), "refine_fused_ms": round(tn, 4), "refine_fused_iters0_ms": round(t0, 4),
             "kernel_iteration_ms": round((kn - k0) / iters, 4), "kernel_ms": round(kn, 4), "kernel_iters0_ms": round(k0, 4),
             "refine_fused_ms_rounds": rn, "refine_fused_iters0_ms_rounds": r0, "kernel_ms_rounds": krn, "kernel_iters0_ms_rounds": kr0,
@@ -394,6 +395,8 @@ def main():
                     help="also time one Levenberg-Marquardt iteration of refine.refine_poses and tik_lm_solve alone")
     ap.add_argument("--refine-fused", action="store_true",
                     help="also time the fused path (refine_poses(fused=True), SMPLX.refine_frames) per LM iteration")
+    ap.add_argument("--robust", type=float, default=0.0, metavar="S",
+                    help="with --refine-fused: the Geman-McClure scale of the data term in metres (0: the plain square)")
     ap.add_argument("--shape-jacobian", action="store_true",
                     help="also time SMPLX.joints_shape_jacobian (COCO-17, all betas)")
     ap.add_argument("--fit-shape", action="store_true",
@@ -411,7 +414,7 @@ def main():
     if a.refine:
         out["refine"] = measure_refine(a.batch, a.steps, a.warmup)
     if a.refine_fused:
-        out["refine_fused"] = measure_refine_fused(a.batch, a.steps, a.warmup)
+        out["refine_fused"] = measure_refine_fused(a.batch, a.steps, a.warmup, robust=a.robust)
     if a.shape_jacobian:
         out["shape_jacobian"] = measure_shape_jacobian(a.batch, a.steps, a.warmup)
     if a.fit_shape:

@@ -219,6 +219,31 @@ int tik_stream_path(tik_stream_t s);
 int tik_stream_set_refine(tik_stream_t s, tik_fk_t fk, const float* betas_host, const float* joint_w_host,
                           int iters, float mu, float smooth, float lam0);
 int tik_stream_raw_pose(tik_stream_t s, float* pose_host);
+/* Imperfect detections. tik_stream_push_conf is tik_stream_push with 17
+ * confidences (host, >= 0). Keypoint k is missing when conf[k] is 0 or one of
+ * its coordinates is NaN or Inf (a non-finite keypoint with positive
+ * confidence counts as confidence 0). The fill runs on the host before the
+ * frame goes to pinned memory: a missing keypoint takes the last value this
+ * stream accepted for it, in absolute coordinates (hold-last; a stated rule,
+ * not a tuned one: nobody has measured it on real detections), so the ring
+ * never holds a non-finite value and the network sees a complete frame.
+ * TIK_E_INVALID, the frame not appended and the stream as if never offered it:
+ * a missing keypoint not seen since create or tik_stream_reset (which clears
+ * the last-seen state), a confidence that is negative, NaN or infinite.
+ * A refining stream keeps W x 17 confidences beside the keypoint ring: the
+ * refine launch reads this push's 17 from pinned host memory, stores them at
+ * the slot of frame count - 1 and refines frame c = count - 1 - h with
+ * keypoint weights conf_c[k] * joint_w[k] (one fp32 multiply); if conf_c[11]
+ * or conf_c[12] is 0 all 17 are 0 and the pose moves only toward the network's
+ * and the previous refined pose. tik_stream_push on such a stream is the push
+ * with confidences of one, and gives the bits it gave before. A stream without
+ * refinement takes tik_stream_push_conf too: the fill only.
+ * tik_stream_set_robust: the robust scale (tik_fk_refine_robust's
+ * robust_sigma) of the refine launch, 0 = off; records the step again like
+ * tik_stream_set_refine, which keeps the scale. Call it between pushes.
+ * TIK_E_INVALID: sigma negative, NaN or infinite. */
+int tik_stream_push_conf(tik_stream_t s, const float* frame_host, const float* conf_host, float* pose_host);
+int tik_stream_set_robust(tik_stream_t s, float sigma);
 /* Debug (TIK_ONLINE_TRACE=1 at create): the last step's per-task timestamps
  * {ticket taken, inputs ready, staged, computed, reduced, stores complete,
  * done, workgroup} (s_memrealtime ticks, 100 MHz; staged .. reduced: gcn and
@@ -602,6 +627,35 @@ int tik_fk_refine(tik_fk_t fk, const float* poses, const float* prior, const flo
                   const float* betas, int betas_ld, const float* joint_w, int joint_w_ld, const int* sel17, int iters,
                   float mu, float smooth, float lam0, int B, float* out_poses, float* out_cost, float* dbg_jac,
                   float* dbg_r, void* stream);
+/* tik_fk_refine on imperfect detections; tik_fk_refine is this call with
+ * (robust_sigma, flags, dbg_w) = (0, 0, NULL), the same instructions and bits.
+ * robust_sigma > 0 (metres) replaces the weighted square of the data term by
+ * Geman-McClure on s_k = |r_k|^2:
+ *   rho(s)      = sigma^2 s / (sigma^2 + s)
+ *   cost(theta) = 1/2 sum_k w_k rho(s_k) + the prior and prev terms as above
+ *   omega_k     = w_k rho'(s_k) = w_k (sigma^2 / (sigma^2 + s_k))^2        (from the current pose's residual)
+ *   (J^T Omega J + (mu + smooth + lambda) I) delta = -(J^T Omega r + mu (theta - theta0) + smooth (theta - thetap))
+ * J^T Omega r is the exact gradient of the robust data term; the matrix is the
+ * Gauss-Newton (IRLS) one: the second-derivative term of rho, which is
+ * negative (it turns the full Hessian indefinite along r_k past s_k =
+ * sigma^2 / 3), is dropped on purpose, so the matrix stays positive
+ * definite. Accept and reject are judged on the true robust cost of the
+ * candidate, and the cost row still never increases. There is no tuned sigma:
+ * 0 (off) is the default everywhere.
+ * flags: TIK_REFINE_SKIP_NONFINITE treats a keypoint with a NaN or Inf
+ * component as missing: weight 0 and a finite target; a frame whose column 11
+ * or 12 is missing has all 17 weights 0 and can move only toward prior and
+ * prev. Without the flag a NaN keypoint behaves as in tik_fk_refine.
+ * dbg_w (B,17) or NULL: the omega_k of the first linearisation (w_k where
+ * robust_sigma = 0), written for any iters like dbg_jac / dbg_r.
+ * TIK_E_INVALID before any device work: whatever tik_fk_refine refuses, a
+ * robust_sigma that is negative, NaN or infinite, a bit of flags other than
+ * the one defined. */
+#define TIK_REFINE_SKIP_NONFINITE 1
+int tik_fk_refine_robust(tik_fk_t fk, const float* poses, const float* prior, const float* prev, const float* kps,
+                         const float* betas, int betas_ld, const float* joint_w, int joint_w_ld, const int* sel17,
+                         int iters, float mu, float smooth, float lam0, int B, float* out_poses, float* out_cost,
+                         float* dbg_jac, float* dbg_r, float robust_sigma, int flags, float* dbg_w, void* stream);
 
 /* ------------------------------------------------------------------------
  * The keypoint loss of a pose and its gradient with respect to the pose in

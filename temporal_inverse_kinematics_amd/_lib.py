@@ -70,6 +70,8 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_stream_path": (_I, (_P,)),
     "tik_stream_set_refine": (_I, (_P, _P, _F, _F, _I, ctypes.c_float, ctypes.c_float, ctypes.c_float)),
     "tik_stream_raw_pose": (_I, (_P, _F)),
+    "tik_stream_push_conf": (_I, (_P, _F, _F, _F)),
+    "tik_stream_set_robust": (_I, (_P, ctypes.c_float)),
     "tik_rotate_root_z": (_I, (_P, _I, _I, ctypes.c_double, _P)),
     "tik_train_windows": (_I, (_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, ctypes.c_ulonglong, _P, _P, _P)),
     "tik_debug_stream_trace": (_I, (_P, ctypes.POINTER(ctypes.c_longlong), _I)),
@@ -91,6 +93,8 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
     "tik_lm_solve_chain": (_I, (_P, _P, _P, _P, _P, _I, _P, _P, ctypes.c_float, ctypes.c_float, _I, _I, _I, _I, _P, _P, _P)),
     "tik_fk_refine": (_I, (_P, _P, _P, _P, _P, _P, _I, _P, _I, ctypes.POINTER(_I), _I, ctypes.c_float, ctypes.c_float,
                            ctypes.c_float, _I, _P, _P, _P, _P, _P)),
+    "tik_fk_refine_robust": (_I, (_P, _P, _P, _P, _P, _P, _I, _P, _I, ctypes.POINTER(_I), _I, ctypes.c_float, ctypes.c_float,
+                                  ctypes.c_float, _I, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P)),
     "tik_fk_keypoint_loss": (_I, (_P, _P, _I, _P, _P, _I, _P, _I, ctypes.POINTER(_I), _P, _I, _P, _P, _I, ctypes.c_float, _I,
                                   _P)),
     "tik_fk_workspace_bytes": (ctypes.c_longlong, (_P,)),

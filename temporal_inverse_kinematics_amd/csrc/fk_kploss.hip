@@ -14,8 +14,9 @@
 //   3  linearize: dR and omega per dof, the 3x3 blocks of J (51,66) in LDS, rel on its rows                   3 barriers
 //   4  thread q < 66: g[q], one FMA chain over the 51 rows in ascending order, (J[i][q] w_i) r_i per term
 //      (lm_accumulate_body's term); the thread writes grad[f][q]
-// Phases 3 and 4 only with grad. One FK state and no lm_dev.h slabs: lds_frame_floats(K, 1) floats of LDS, 29.5 KB
-// with 4 skinning entries per vertex and 39.7 KB with the dense table (lm_refine_kernel: 48.0 and 58.4 KB).
+// Phases 3 and 4 only with grad. One FK state and no lm_dev.h slabs: lds_frame_floats(K, 1) floats of LDS, 30464 B
+// with 4 skinning entries per vertex and 40880 B with the dense table (lm_refine_kernel: 48220 and 58636 B). The slab of
+// robust row weights (Lds::ow, 208 B) is lm_refine_kernel's; here it is carved and not used.
 // Every sum has a fixed order, no atomics, every output element has one writer, and a workgroup sees only its
 // own frame: a frame's bits do not depend on B, on its place in the batch or on rows.
 #include <cmath>
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(LM_T) void fk_kploss_kernel(FkKpLossArgs a) {
     const int K = skin_count(a);
     const Lds s(smem, K, 1);
     int dj, par;
-    frame_setup(a, s, a.poses + f * a.poses_ld, nullptr, nullptr, false, a.kps + f * M, f, K, 1, dj, par);
+    frame_setup(a, s, a.poses + f * a.poses_ld, nullptr, nullptr, false, a.kps + f * M, nullptr, false, f, K, 1, dj, par);
     float* S = s.state(0);
     fk_eval(a, s, S, s.th, dj, par, K);
     if (a.loss && tid < 64) {

@@ -22,6 +22,8 @@ struct LmRefineStream {
     const int* count;    // frames pushed so far, this step's included: the frame refined is c = count - 1 - h
     const float* ring;   // W frames of 51 floats; frame c at slot c % W
     int W, h;
+    const float* conf_host;   // pinned: the 17 confidences of this push (ones for a plain tik_stream_push)
+    float* cring;        // W rows of 17 confidences beside the ring, the same slots; the kernel stores frame count - 1's
     float* prev;         // (66) the previous refined pose
     int* have;           // non-zero once prev holds one (cleared by tik_stream_reset)
     float* pose_host;    // pinned: the refined pose, then
@@ -43,7 +45,10 @@ struct LmRefineArgs : FkSelArgs {   // B frames; n_sel = 17, sel = the keypoints
     const int *parents, *depth;
     const unsigned long long* anc;
     float *out_poses, *out_cost, *dbg_jac, *dbg_r;
-    int nv;                          // keypoints that are a vertex of the body (the others are chain joints)
+    float sigma;                     // robust scale in metres; 0: the plain weighted square
+    int flags;                       // TIK_REFINE_* (include/tik.h)
+    float* dbg_w;                    // (B,17) or null: the IRLS weights of the first linearisation
+    int nv;                         // keypoints that are a vertex of the body (the others are chain joints)
     signed char slot[LMR_COLS];      // column s: its vertex slot, or -1
     LmRefineStream st;
 };
@@ -52,6 +57,8 @@ struct LmRefineArgs : FkSelArgs {   // B frames; n_sel = 17, sel = the keypoints
 // lm_check_range. sel17: 17 joint indices, or null = LMR_COCO_SMPLX. TIK_E_INVALID names the value.
 int lm_refine_model_args(const tik_fk* fk, const char* who, const int* sel17, int iters, float mu, float smooth, float lam0,
                          LmRefineArgs& a);
+// The robust scale of an entry point (`who`): >= 0 and finite, else TIK_E_INVALID
+int lm_refine_check_sigma(const char* who, float sigma);
 // B workgroups; a's pointers must be set. -> TIK_OK or TIK_E_HIP
 int lm_refine_launch(const LmRefineArgs& a, void* stream);
 

@@ -28,7 +28,7 @@ struct Lds {
     __device__ float* state(int i) const { return st0 + i * ST_FLOATS; }
     float *G, *Jr;                         // G_j (55,12), the rest joints (55,3): chain scratch
     float *TR, *dR, *om;                   // linearisation: T.R per vertex (17,9), dR (22,3,9), omega (22,3,3)
-    float *tgt, *rw;                       // rel(kps) (51), the row weights (51)
+    float *tgt, *rw, *ow;                  // rel(kps) (51), the row weights (51), the robust (IRLS) row weights (51)
     float *th, *th0, *thp, *cand, *d0, *dp;   // poses (66 each): current, prior, previous, candidate, th - th0, th - thp
     float *beta, *c;                       // betas (32), [0] a cost
     int *pv, *ancm;                        // vertex ids (17), the 22 low bits of anc (55)
@@ -42,7 +42,7 @@ struct Lds {
         st0 = take(NS * ST_FLOATS);
         G = take(NJ * 12); Jr = take(NJ * 3);
         TR = take(NC * 9); dR = take(ND * 27); om = take(ND * 9);
-        tgt = take(M); rw = take(M);
+        tgt = take(M); rw = take(M); ow = take(M);
         th = take(N); th0 = take(N); thp = take(N); cand = take(N); d0 = take(N); dp = take(N);
         beta = take(32); c = take(4);
         pv = reinterpret_cast<int*>(take(NC)); ancm = reinterpret_cast<int*>(take(NJ));
@@ -55,7 +55,7 @@ struct Lds {
 };
 // floats of LDS without lm_dev.h's slabs
 __host__ __device__ constexpr size_t lds_frame_floats(int K, int NS) {
-    return (size_t)NS * ST_FLOATS + r4(NJ * 12) + r4(NJ * 3) + r4(NC * 9) + r4(ND * 27) + r4(ND * 9) + 2 * r4(M) + 6 * r4(N) + 32 + 4 +
+    return (size_t)NS * ST_FLOATS + r4(NJ * 12) + r4(NJ * 3) + r4(NC * 9) + r4(ND * 27) + r4(ND * 9) + 3 * r4(M) + 6 * r4(N) + 32 + 4 +
            3 * r4(NC) + r4(NJ) + 3 * (size_t)r4(NC * K) + r4(M * N);
 }
 __host__ __device__ constexpr size_t lds_floats(int K) { return lds_frame_floats(K, 2) + lm_lds_floats(N); }
@@ -68,11 +68,19 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// neither NaN nor Inf, from the bits (no floating-point compile option can fold the test away)
+__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
 // The frame's constants into LDS, by the whole workgroup: poses, prior, prev (66 each; the last two or null) and kps
 // (17,3) are the frame's own rows; f is its row of betas and joint_w; tie: thp = prev. Also thread j's tree depth
 // and parent (-1 past the joints), and the feature tail of the NS states. Ends on a barrier.
+// conf (17, or null): a stream's confidences of this frame; keypoint k then weighs conf[k] * joint_w[k], and nothing
+// does where conf[11] or conf[12] is 0. skip (TIK_REFINE_SKIP_NONFINITE; refine._frame_weights' rule): a keypoint
+// with a non-finite component weighs 0 and its target is taken as 0, and without both of columns 11 and 12 every
+// weight of the frame is 0. With conf null and skip false: the arithmetic without them.
 __device__ __forceinline__ void frame_setup(const LmRefineArgs& a, const Lds& s, const float* poses, const float* prior, const float* prev,
-                                            bool tie, const float* kps, size_t f, int K, int NS, int& dj, int& par) {
+                                            bool tie, const float* kps, const float* conf, bool skip, size_t f, int K, int NS, int& dj,
+                                            int& par) {
     const int tid = threadIdx.x;
     if (tid < N) {
         const float t = poses[tid];
@@ -81,9 +89,19 @@ __device__ __forceinline__ void frame_setup(const LmRefineArgs& a, const Lds& s,
         s.thp[tid] = tie ? prev[tid] : 0.f;
     }
     if (tid < M) {
-        const int c = tid % 3;
-        s.tgt[tid] = kps[tid] - 0.5f * (kps[33 + c] + kps[36 + c]);
-        s.rw[tid] = a.joint_w ? a.joint_w[f * a.joint_w_ld + tid / 3] : 1.f;
+        const int c = tid % 3, k = tid / 3;
+        float x = kps[tid], ha = kps[33 + c], hb = kps[36 + c];
+        float w = a.joint_w ? a.joint_w[f * a.joint_w_ld + k] : 1.f;
+        if (conf) w = (conf[11] == 0.f || conf[12] == 0.f) ? 0.f : conf[k] * w;
+        if (skip) {
+            const bool seen = finite_bits(kps[3 * k]) && finite_bits(kps[3 * k + 1]) && finite_bits(kps[3 * k + 2]);
+            const bool sa = finite_bits(kps[33]) && finite_bits(kps[34]) && finite_bits(kps[35]);
+            const bool sb = finite_bits(kps[36]) && finite_bits(kps[37]) && finite_bits(kps[38]);
+            x = seen ? x : 0.f; ha = sa ? ha : 0.f; hb = sb ? hb : 0.f;
+            w = (seen && sa && sb) ? w : 0.f;
+        }
+        s.tgt[tid] = x - 0.5f * (ha + hb);
+        s.rw[tid] = w;
     }
     if (tid < 32) s.beta[tid] = (a.betas && tid < a.nb) ? a.betas[f * a.betas_ld + tid] : 0.f;
     if (tid == 64) {   // the selection out of the kernel arguments by constant indices (scalar loads, no private copy)
@@ -330,6 +348,24 @@ __device__ __forceinline__ float weighted_sq(const Lds& s, const float* S) {
     if (tid < NC) {
         const float* r = S + ST_R + 3 * tid;
         p = s.rw[3 * tid] * fmaf(r[2], r[2], fmaf(r[1], r[1], r[0] * r[0]));
+    }
+    return wave_sum(p);
+}
+
+// Geman-McClure on s = |r_k|^2 with sig2 = sigma^2: rho(s) = sig2 s / (sig2 + s), rho'(s) = (sig2 / (sig2 + s))^2
+__device__ __forceinline__ float sq_norm3(const float* r) { return fmaf(r[2], r[2], fmaf(r[1], r[1], r[0] * r[0])); }
+// w_k rho'(s_k) of keypoint k of state S: the IRLS weight of its three rows
+__device__ __forceinline__ float robust_weight(const Lds& s, const float* S, int k, float sig2) {
+    const float t = sig2 / (sig2 + sq_norm3(S + ST_R + 3 * k));
+    return s.rw[3 * k] * (t * t);
+}
+// sum_k w_k rho(|r_k|^2) of state S, as weighted_sq
+__device__ __forceinline__ float weighted_rho(const Lds& s, const float* S, float sig2) {
+    const int tid = threadIdx.x;
+    float p = 0.f;
+    if (tid < NC) {
+        const float q = sq_norm3(S + ST_R + 3 * tid);
+        p = s.rw[3 * tid] * (sig2 * q / (sig2 + q));
     }
     return wave_sum(p);
 }

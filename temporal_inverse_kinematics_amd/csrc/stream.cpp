@@ -41,6 +41,7 @@ StreamEnv read_env() {
 
 // every G / T output carries its launch's tag in its sign bit (online.hip): tag 1 before launch 0
 constexpr int ACT_TAG1 = (int)0x80000000u;
+constexpr int CONF_ONE = 0x3f800000;   // 1.0f: the confidence of a frame pushed without one
 
 template <class T>
 int host_alloc(T** p, size_t n, unsigned flags) {
@@ -231,7 +232,18 @@ int tik_stream_reset(tik_stream_t s) {
     if (s->host_rdone) *s->host_rdone = 0;
     s->pushed = 0;
     s->dcount = 0;
+    s->last.clear();   // no keypoint has been seen; the confidence ring's slots are written before they are read
     return TIK_OK;
+}
+
+int tik_stream_set_robust(tik_stream_t s, float sigma) {
+    if (!s) return fail(TIK_E_INVALID, "tik_stream_set_robust: null stream");
+    if (int rc = tik::lm_refine_check_sigma("tik_stream_set_robust", sigma)) return rc;
+    HIP_TRY(hipStreamSynchronize(s->st));   // idle between pushes
+    s->rsigma = sigma;
+    if (!s->refining()) return TIK_OK;      // kept for a later tik_stream_set_refine
+    s->rargs.sigma = sigma;
+    return s->exec ? capture_step(s) : TIK_OK;
 }
 
 int tik_stream_set_refine(tik_stream_t s, tik_fk_t fk, const float* betas_host, const float* joint_w_host, int iters, float mu,
@@ -255,12 +267,17 @@ int tik_stream_set_refine(tik_stream_t s, tik_fk_t fk, const float* betas_host, 
         if ((betas_host && a.nb > 0 && (rc = s->rbetas.upload(std::vector<float>(betas_host, betas_host + a.nb)))) ||
             (joint_w_host && (rc = s->rjw.upload(std::vector<float>(joint_w_host, joint_w_host + tik::LMR_COLS)))) ||
             (rc = s->rprev.reserve(tik::LMR_N)) || (rc = s->rhave.reserve(1)) ||
+            (rc = s->cring.reserve((size_t)s->lim.W * tik::LMR_COLS)) ||
+            (!s->host_conf && (rc = host_alloc(&s->host_conf, tik::LMR_COLS, hipHostMallocDefault))) ||
             (!s->host_refined && (rc = host_alloc(&s->host_refined, tik::LMR_N, hipHostMallocCoherent))) ||
             (!s->host_rdone && ((rc = host_alloc(&done, 1, hipHostMallocCoherent)) || (s->host_rdone = done, 0))))
             return rc;
         HIP_TRY(hipMemsetAsync(s->rhave.p, 0, sizeof(int), s->st));
         HIP_TRY(hipMemsetAsync(s->rprev.p, 0, sizeof(float) * tik::LMR_N, s->st));
+        // the frames already in the ring were pushed without the refine launch: confidence one
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->cring.p), CONF_ONE, s->cring.n, s->st));
         HIP_TRY(hipStreamSynchronize(s->st));
+        for (int k = 0; k < tik::LMR_COLS; ++k) s->host_conf[k] = 1.f;
         *s->host_rdone = s->dcount;
         a.B = 1;
         a.poses = s->online ? s->onl_pose : s->poses.p;   // the step's device copy of pose row 0 (the dataflow kernel's carries no tag)
@@ -268,7 +285,11 @@ int tik_stream_set_refine(tik_stream_t s, tik_fk_t fk, const float* betas_host, 
         a.joint_w = joint_w_host ? s->rjw.p : nullptr;
         a.st.count = s->count.p; a.st.ring = s->ring.p; a.st.W = s->lim.W; a.st.h = s->lim.h;
         a.st.prev = s->rprev.p; a.st.have = s->rhave.p;
-        if ((rc = device_view(&a.st.pose_host, s->host_refined)) || (rc = device_view(&a.st.done_host, s->host_rdone))) return rc;
+        a.st.cring = s->cring.p;
+        a.sigma = s->rsigma;
+        if ((rc = device_view(&a.st.pose_host, s->host_refined)) || (rc = device_view(&a.st.done_host, s->host_rdone)) ||
+            (rc = device_view(&a.st.conf_host, s->host_conf)))
+            return rc;
         fk_retain(fk);
     }
     if (s->rfk) fk_release(s->rfk);

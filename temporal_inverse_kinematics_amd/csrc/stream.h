@@ -60,6 +60,10 @@ struct tik_stream {
     tik::LmRefineArgs rargs{};     // the launch's arguments; rargs.iters == 0: no refinement
     tik_host::DevBuf rbetas, rjw, rprev;   // betas (nb), keypoint weights (17), the previous refined pose (66)
     tik_host::DevIBuf rhave;       // non-zero once rprev holds a pose
+    float rsigma = 0.f;            // tik_stream_set_robust's scale; copied into rargs whenever the step is recorded
+    tik_host::DevBuf cring;        // W rows of 17 confidences beside the ring (a refining stream's)
+    float* host_conf = nullptr;    // pinned: this push's confidences, read by the refine launch (ones for a plain push)
+    tik_stream_plan::LastSeen last;   // per keypoint, the last value the stream accepted (tik_stream_push_conf's fill)
     float* host_refined = nullptr;         // pinned, coherent: the refined pose
     volatile int* host_rdone = nullptr;    // pinned, coherent: the frame count after each refined step
     bool refining() const { return rargs.iters > 0; }
@@ -71,6 +75,7 @@ struct tik_stream {
         if (host_pose) (void)hipHostFree(host_pose);
         if (host_done) (void)hipHostFree(const_cast<int*>(host_done));
         if (host_refined) (void)hipHostFree(host_refined);
+        if (host_conf) (void)hipHostFree(host_conf);
         if (host_rdone) (void)hipHostFree(const_cast<int*>(host_rdone));
         if (st) (void)hipStreamDestroy(st);
         if (model) tik_host::model_release(model);

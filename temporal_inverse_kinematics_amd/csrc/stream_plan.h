@@ -12,8 +12,10 @@
 //             the head gives n_out / n_in per layer; from them follow the one
 //             activation buffer's layout, the task list and the counter words
 //   packers   the kernel's weight layouts, as pure functions of host vectors
+//   frames    what a push checks before it takes a frame (check_frame), and the
+//             hold-last fill of a frame pushed with confidences (fill_frame)
 //
-// Stands alone in tests/test_stream_plan_host.py.
+// Stands alone in tests/test_stream_plan_host.py and tests/test_lm_robust_host.py.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -98,6 +100,45 @@ inline int check_frame(const float* frame) {
     memcpy(&u, frame + i, sizeof u);
     return fail(TIK_E_INVALID, "tik_stream_push: frame value %d (joint %d, coordinate %d) is %s; the frame was not appended", i, i / 3, i % 3,
                 (u & 0x007fffffu) ? "NaN" : "infinite");
+}
+
+// ---------------------------------------------------------------- a frame with confidences (any step)
+// tik_stream_push_conf's rule, on the host before anything is copied or enqueued. Keypoint k is missing when
+// conf[k] is 0 or one of its coordinates is not finite (a non-finite keypoint with positive confidence counts as
+// confidence 0). The network cannot take a hole (check_frame), so a missing keypoint is filled with the last
+// value this stream accepted for it, in absolute coordinates: hold-last. That is a stated rule, not a tuned
+// one. A keypoint that is missing and was never seen since create or reset refuses the frame, as check_frame
+// refuses a NaN; so does a confidence that is negative or not finite. A refusal changes nothing.
+struct LastSeen {
+    float kp[FRAME] = {};
+    bool seen[V] = {};
+    void clear() { *this = LastSeen{}; }
+};
+
+// frame (51) and conf (17) -> out_frame (51, finite) and out_conf (17: 0 where missing, else conf). `last` is read only.
+inline int fill_frame(const float* frame, const float* conf, const LastSeen& last, float* out_frame, float* out_conf) {
+    const int bad = first_nonfinite(conf, V);
+    if (bad >= 0) return fail(TIK_E_INVALID, "tik_stream_push_conf: confidence %d is not finite; the frame was not appended", bad);
+    for (int k = 0; k < V; ++k)
+        if (!(conf[k] >= 0.f))
+            return fail(TIK_E_INVALID, "tik_stream_push_conf: confidence %d is negative (%g); the frame was not appended", k, (double)conf[k]);
+    for (int k = 0; k < V; ++k) {
+        const bool missing = conf[k] == 0.f || first_nonfinite(frame + 3 * k, 3) >= 0;
+        if (missing && !last.seen[k])
+            return fail(TIK_E_INVALID, "tik_stream_push_conf: joint %d is missing and has not been seen since the stream was created or "
+                        "reset; the frame was not appended", k);
+        const float* src = missing ? last.kp + 3 * k : frame + 3 * k;
+        for (int c = 0; c < 3; ++c) out_frame[3 * k + c] = src[c];
+        out_conf[k] = missing ? 0.f : conf[k];
+    }
+    return TIK_OK;
+}
+
+// the frame the stream accepted (finite: check_frame or fill_frame passed) becomes the last value of every keypoint
+// (a filled one repeats what was held, so after any accepted frame every keypoint has been seen)
+inline void accept_frame(LastSeen& last, const float* frame) {
+    for (int k = 0; k < V; ++k) last.seen[k] = true;
+    memcpy(last.kp, frame, sizeof last.kp);
 }
 
 // ---------------------------------------------------------------- the dataflow step

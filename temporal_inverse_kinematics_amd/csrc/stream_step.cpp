@@ -5,7 +5,9 @@
 // (TIK_ONLINE=0, or a model that kernel does not cover, stream_plan.h): ring
 // append, window gather, the layered IK forward on the whole window, the pose
 // copy. Either is one hipGraph replay on the private stream when the stream
-// was created with use_graph (stream.cpp).
+// was created with use_graph (stream.cpp). tik_stream_push_conf is the same push
+// behind the host fill of stream_plan.h (fill_frame): the frame it hands on is
+// finite, and its 17 confidences go to pinned memory for the refine launch.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -40,11 +42,12 @@ int stream_record_step(tik_stream* s) {
 
 }  // namespace tik_host
 
-extern "C" int tik_stream_push(tik_stream_t s, const float* frame_host, float* pose_host) {
-    if (!s || !frame_host) return fail(TIK_E_INVALID, "tik_stream_push: bad arguments");
-    // a NaN or Inf is refused here: nothing is copied or enqueued, ring, count and tags stay as they were
-    if (const int rc = sp::check_frame(frame_host)) return rc;
-    memcpy(s->host_frame, frame_host, sizeof(float) * sp::FRAME);
+// one step on a frame that passed its check: frame (51, finite) and, for a refining stream, conf (17) or null = ones
+static int push_frame(tik_stream_t s, const float* frame, const float* conf, float* pose_host) {
+    sp::accept_frame(s->last, frame);
+    memcpy(s->host_frame, frame, sizeof(float) * sp::FRAME);
+    if (s->host_conf)
+        for (int k = 0; k < sp::V; ++k) s->host_conf[k] = conf ? conf[k] : 1.f;
     if (s->exec) {
         HIP_TRY(hipGraphLaunch(s->exec, s->st));
     } else {
@@ -76,6 +79,21 @@ extern "C" int tik_stream_push(tik_stream_t s, const float* frame_host, float* p
     const int valid = s->pushed > s->lim.h;   // frame pushed-1-h >= 0 solved
     if (valid && pose_host) memcpy(pose_host, s->refining() ? s->host_refined : s->host_pose, sizeof(float) * sp::POSE_DIM);
     return valid;
+}
+
+extern "C" int tik_stream_push(tik_stream_t s, const float* frame_host, float* pose_host) {
+    if (!s || !frame_host) return fail(TIK_E_INVALID, "tik_stream_push: bad arguments");
+    // a NaN or Inf is refused here: nothing is copied or enqueued, ring, count and tags stay as they were
+    if (const int rc = sp::check_frame(frame_host)) return rc;
+    return push_frame(s, frame_host, nullptr, pose_host);
+}
+
+extern "C" int tik_stream_push_conf(tik_stream_t s, const float* frame_host, const float* conf_host, float* pose_host) {
+    if (!s || !frame_host || !conf_host) return fail(TIK_E_INVALID, "tik_stream_push_conf: bad arguments");
+    // the fill on the host (stream_plan.h): the ring never holds a non-finite value; a refusal changes nothing
+    float frame[sp::FRAME], conf[sp::V];
+    if (const int rc = sp::fill_frame(frame_host, conf_host, s->last, frame, conf)) return rc;
+    return push_frame(s, frame, conf, pose_host);
 }
 
 extern "C" int tik_stream_raw_pose(tik_stream_t s, float* pose_host) {

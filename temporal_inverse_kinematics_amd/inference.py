@@ -7,7 +7,7 @@ reference, each window's output frame 0 is the solution for frame idx
 CLI (README.md:24-26):
     python -m temporal_inverse_kinematics_amd.inference <moveai_3d.npz> [SMPLX_DIR]
         [--ckpt model.ckpt] [--win-size 64] [--out poses.npy] [--check] [--refine N]
-        [--fit-shape R] [--smooth W]
+        [--fit-shape R] [--smooth W] [--robust S]
 Without --ckpt the seeded synthetic weights are used (the trained checkpoint
 is not distributed with the reference: .MISSING_LARGE_BLOBS:2).
 """
@@ -71,7 +71,8 @@ def fk_check(poses, seq_3d_kps, smplx_model, betas=None) -> dict:
 
 
 def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = None, win_size: int = 64,
-             device="cuda", check: bool = False, refine: int = 0, fit_shape: int = 0, smooth: float = 0.0):
+             device="cuda", check: bool = False, refine: int = 0, fit_shape: int = 0, smooth: float = 0.0,
+             robust: float = 0.0):
     """inference.run_test:110-145: moveai npz -> COCO -> IK -> (optional) SMPL-X FK.
     check=True (with an SMPL-X dir): the result gains "fk_check" (fk_check above).
     refine=N > 0 (with an SMPL-X dir): N Levenberg-Marquardt iterations on the
@@ -85,7 +86,11 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
     neighbouring frames with 1/2 W sum_f |theta_{f+1} - theta_f|^2
     (refine.refine_smooth, the track one sequence), alone or inside the rounds
     of fit_shape; the output keys are those of refine. smooth=0 leaves every
-    output as it is."""
+    output as it is.
+    robust=S > 0 (with an SMPL-X dir and refine=N > 0, without fit_shape and
+    smooth): the N iterations run in the fused kernel (refine_poses(fused=True))
+    with the Geman-McClure scale S in metres and non-finite keypoints treated
+    as missing. There is no tuned S; robust=0 leaves every output as it is."""
     if refine < 0:
         raise ValueError(f"refine must be >= 0, got {refine}")
     if fit_shape < 0:
@@ -98,6 +103,11 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
         raise ValueError("smooth needs an SMPL-X dir (or 'synthetic') and refine=N > 0, the pose iterations it smooths")
     if refine and not smplx_dir:
         raise ValueError("refine needs an SMPL-X dir (or 'synthetic'): the refinement runs the FK")
+    if not (robust >= 0 and robust < float("inf")):
+        raise ValueError(f"robust must be >= 0 and finite, got {robust}")
+    if robust and (not (smplx_dir and refine > 0) or fit_shape or smooth):
+        raise ValueError("robust needs an SMPL-X dir (or 'synthetic') and refine=N > 0, and neither fit_shape nor smooth: "
+                         "the robust term lives in the fused kernel, not in the launched loops")
     d = np.load(npz_path, allow_pickle=False)
     # the moveai_3d -> COCO conversion on the device (one gather kernel, bit-identical to the host form)
     seq = kp.moveai3d_to_coco_device(torch.as_tensor(np.ascontiguousarray(d["joints_3d"], dtype=np.float32),
@@ -131,6 +141,9 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
             from .refine import refine_poses, refine_smooth
             if smooth:
                 result["poses_refined"] = refine_smooth(poses, result["coco"], models["male"], smooth, iters=refine)["poses"]
+            elif robust:
+                result["poses_refined"] = refine_poses(poses, result["coco"], models["male"], iters=refine, fused=True,
+                                                       robust_sigma=robust, skip_nonfinite=True)["poses"]
             else:
                 result["poses_refined"] = refine_poses(poses, result["coco"], models["male"], iters=refine)["poses"]
             if check:
@@ -156,6 +169,9 @@ def build_parser():
     p.add_argument("--smooth", type=float, default=0.0, metavar="W",
                    help="with SMPLX_DIR and --refine N: the pose iterations tie neighbouring frames with the weight W on "
                         "the squared difference of their poses (one block-tridiagonal solve for the whole track)")
+    p.add_argument("--robust", type=float, default=0.0, metavar="S",
+                   help="with SMPLX_DIR and --refine N (without --fit-shape and --smooth): the iterations run in the fused "
+                        "kernel with a Geman-McClure data term of scale S metres, and non-finite keypoints count as missing")
     return p
 
 
@@ -173,8 +189,10 @@ def main(argv=None):
         p.error("--fit-shape R needs R >= 0, an SMPLX_DIR and --refine N with N > 0 (the pose iterations per round)")
     if not a.smooth >= 0 or (a.smooth and not (a.smplx_dir and a.refine > 0)):
         p.error("--smooth W needs W >= 0, an SMPLX_DIR and --refine N with N > 0 (the pose iterations it smooths)")
+    if not (a.robust >= 0 and a.robust < float("inf")) or (a.robust and (not (a.smplx_dir and a.refine > 0) or a.fit_shape or a.smooth)):
+        p.error("--robust S needs S >= 0, an SMPLX_DIR and --refine N with N > 0, and neither --fit-shape nor --smooth")
     r = run_test(a.npz, a.smplx_dir, a.ckpt, a.win_size, check=a.check, refine=a.refine, fit_shape=a.fit_shape,
-                 smooth=a.smooth)
+                 smooth=a.smooth, robust=a.robust)
     if a.out:
         np.save(a.out, r.get("poses_refined", r["poses"]))
         if "betas" in r:

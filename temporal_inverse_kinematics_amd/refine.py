@@ -55,7 +55,7 @@ import numpy as np
 import torch
 
 from . import inference
-from .smplx_fk import (LM_RUN, lm_accumulate, lm_chain_starts, lm_chain_workspace_floats, lm_partial_width, lm_solve,
+from .smplx_fk import (LM_RUN, check_robust_args, lm_accumulate, lm_chain_starts, lm_chain_workspace_floats, lm_partial_width, lm_solve,
                        lm_solve_chain, lm_solve_sum)
 
 NUM_DOF = 66
@@ -99,6 +99,16 @@ def _check_joint_weight(joint_weight, F=None):
         raise ValueError(f"joint_weight must be {' or '.join(map(str, shapes))} non-negative values (COCO order), "
                          f"got shape {w.shape}")
     return w
+
+
+def check_fused_options(fused, robust_sigma, skip_nonfinite):
+    """refine_poses' options for imperfect detections -> (sigma, skip). They exist in the fused kernel only: either
+    one given with fused=False is a ValueError, as is a robust_sigma that is negative or not finite."""
+    sigma, flags = check_robust_args(robust_sigma, skip_nonfinite)
+    if not fused and (sigma > 0.0 or flags):
+        raise ValueError("robust_sigma and skip_nonfinite need fused=True: the launched loops have no robust term "
+                         "(refine_smooth treats non-finite keypoints as missing on its own)")
+    return sigma, bool(flags)
 
 
 def _check_prior_poses(prior_poses, F):
@@ -243,7 +253,8 @@ def _lm_loop(th, cost, lam, iters, step, cost_of, frames_of):
 
 # ---------------------------------------------------------------- the drivers
 def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, prior_weight: float = 1e-2,
-                 joint_weight=None, lam0: float = 1e-2, prior_poses=None, fused: bool = False) -> dict:
+                 joint_weight=None, lam0: float = 1e-2, prior_poses=None, fused: bool = False, robust_sigma: float = 0.0,
+                 skip_nonfinite: bool = False) -> dict:
     """poses (F,66) solved by the IK, seq_3d_kps (F,17,3) COCO -> {"poses": (F,66)
     float32 numpy, "cost": (iters+1, F) host array of the cost per frame}
     (cost[0] is theta0's, each later row the accepted pose's after that
@@ -267,11 +278,16 @@ def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, pr
     for bit. The default path and its bits are untouched. Measured at 4096
     frames the launched path is the faster one per iteration (0.70 against
     1.38 ms): the fused kernel is for the stream and for calls
-    that launches, not throughput, bound."""
+    that launches, not throughput, bound.
+
+    robust_sigma > 0 and skip_nonfinite=True (fused=True only, ValueError
+    otherwise): SMPLX.refine_frames' Geman-McClure data term, and non-finite
+    keypoints treated as missing instead of freezing their frame."""
     F = _check_frames(poses, seq_3d_kps)
     _check_lm_scalars(iters, prior_weight, lam0)
     w = _check_joint_weight(joint_weight)
     _check_prior_poses(prior_poses, F)
+    sigma, skip = check_fused_options(fused, robust_sigma, skip_nonfinite)
     iters, pw = int(iters), float(prior_weight)
     th_all, pr_all, kps, beta = _upload(smplx_model, poses, seq_3d_kps, prior_poses, betas)
     dev = th_all.device
@@ -283,7 +299,8 @@ def refine_poses(poses, seq_3d_kps, smplx_model, betas=None, iters: int = 10, pr
         for s, n in _chunks(F):
             th, cost = smplx_model.refine_frames(_rows(th_all, s, n), _rows(kps, s, n), betas=beta,
                                                  prior=None if prior_poses is None else _rows(pr_all, s, n),
-                                                 joint_weight=wj, iters=iters, mu=pw, lam0=float(lam0))
+                                                 joint_weight=wj, iters=iters, mu=pw, lam0=float(lam0), robust_sigma=sigma,
+                                                 skip_nonfinite=skip)
             out.append(th)
             hist.append(cost.t().contiguous())
         return {"poses": _joined(out, 0).cpu().numpy(), "cost": _joined(hist, 1).cpu().numpy()}

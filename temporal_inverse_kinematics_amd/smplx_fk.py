@@ -252,6 +252,19 @@ def check_refine_scalars(iters, mu, smooth, lam0):
     return int(iters), mu, smooth, lam0
 
 
+REFINE_SKIP_NONFINITE = 1        # include/tik.h, TIK_REFINE_SKIP_NONFINITE
+
+
+def check_robust_args(robust_sigma, skip_nonfinite=False):
+    """The options of refine_frames for imperfect detections: robust_sigma >= 0 and finite (metres; 0 = the plain
+    weighted square), skip_nonfinite a flag -> (sigma float, flags int for tik_fk_refine_robust). ValueError
+    otherwise; neither the library nor the device is touched."""
+    sigma = float(robust_sigma)
+    if not (sigma >= 0.0 and sigma < 3.0e18):   # NaN fails; sigma^2 must stay finite in float32
+        raise ValueError(f"robust_sigma must be >= 0 and finite (0 = off), got {robust_sigma}")
+    return sigma, REFINE_SKIP_NONFINITE if skip_nonfinite else 0
+
+
 def resolve_refine_select(select, num_joints: int):
     """The 17 keypoints of refine_frames as joint indices: "coco" or 17 ints, each a chain joint (< 55) or a
     single-vertex joint (55 .. 75). ValueError otherwise (a landmark of three vertices included)."""
@@ -578,7 +591,7 @@ class SMPLX:
 
     def refine_frames(self, poses: torch.Tensor, kps: torch.Tensor, betas=None, prior=None, prev=None, joint_weight=None,
                       iters: int = 10, mu: float = 1e-2, smooth: float = 0.0, lam0: float = 1e-2, select="coco",
-                      debug: bool = False):
+                      debug: bool = False, robust_sigma: float = 0.0, skip_nonfinite: bool = False):
         """The whole Levenberg-Marquardt refinement of B frames in one launch
         (tik_fk_refine, one workgroup per frame): poses (B,66) the start, kps
         (B,17,3) -> (poses (B,66), cost (B, iters+1)); with debug=True also the
@@ -592,10 +605,20 @@ class SMPLX:
         contiguous float32 on the device. select: "coco" or 17 joint indices,
         chain joints or single-vertex joints (columns 11 and 12 the root pair).
         A frame's bits do not depend on B or on its place in the batch.
+        robust_sigma > 0 (metres; tik_fk_refine_robust): the data term becomes
+        1/2 sum_k w_k rho(|r_k|^2), rho(s) = sigma^2 s / (sigma^2 + s)
+        (Geman-McClure), solved as IRLS with weights w_k (sigma^2 / (sigma^2 +
+        |r_k|^2))^2, accept and reject on the true robust cost; debug=True then
+        also returns those weights of the first linearisation (B,17). There is
+        no tuned sigma; 0 is off and runs today's arithmetic. skip_nonfinite=True:
+        a keypoint with a NaN or Inf component is missing (weight 0), and a
+        frame without column 11 or 12 has all weights 0; off, such a frame comes
+        back unchanged with a NaN cost row.
         ValueError before the device is touched: a bad scalar (mu <= 0, smooth <
-        0, lam0 <= 0, iters < 0), a wrong shape, a non-contiguous tensor, a
-        landmark of three vertices in the selection."""
+        0, lam0 <= 0, iters < 0, robust_sigma < 0 or not finite), a wrong shape, a
+        non-contiguous tensor, a landmark of three vertices in the selection."""
         iters, mu, smooth, lam0 = check_refine_scalars(iters, mu, smooth, lam0)
+        sigma, flags = check_robust_args(robust_sigma, skip_nonfinite)
         sel = resolve_refine_select(select, self.num_joints)
         B, betas_ld, jw_ld = _check_refine_tensors(self.num_betas, poses, kps, betas, prior, prev, joint_weight)
         _lib.require_gpu(poses, kps, betas, prior, prev, joint_weight)
@@ -604,12 +627,16 @@ class SMPLX:
         cost = torch.empty((B, iters + 1), device=dev, dtype=torch.float32)
         jac = torch.empty((B, 3 * REFINE_KPS, REFINE_DOF), device=dev, dtype=torch.float32) if debug else None
         r = torch.empty((B, 3 * REFINE_KPS), device=dev, dtype=torch.float32) if debug else None
+        w = torch.empty((B, REFINE_KPS), device=dev, dtype=torch.float32) if debug and sigma > 0 else None
         csel = (_lib.ctypes.c_int * REFINE_KPS)(*sel)
-        _lib.check(_lib.load().tik_fk_refine(self._h, poses.data_ptr(), _lib.ptr(prior), _lib.ptr(prev), kps.data_ptr(),
-                                             _lib.ptr(betas), betas_ld, _lib.ptr(joint_weight), jw_ld, csel, iters, mu, smooth,
-                                             lam0, B, out.data_ptr(), cost.data_ptr(), _lib.ptr(jac), _lib.ptr(r),
-                                             _lib.stream_of(poses)), "SMPLX.refine_frames")
-        return (out, cost, jac, r) if debug else (out, cost)
+        # tik_fk_refine is this call with (0, 0, NULL)
+        _lib.check(_lib.load().tik_fk_refine_robust(self._h, poses.data_ptr(), _lib.ptr(prior), _lib.ptr(prev), kps.data_ptr(),
+                                                    _lib.ptr(betas), betas_ld, _lib.ptr(joint_weight), jw_ld, csel, iters, mu,
+                                                    smooth, lam0, B, out.data_ptr(), cost.data_ptr(), _lib.ptr(jac), _lib.ptr(r),
+                                                    sigma, flags, _lib.ptr(w), _lib.stream_of(poses)), "SMPLX.refine_frames")
+        if not debug:
+            return out, cost
+        return (out, cost, jac, r) if w is None else (out, cost, jac, r, w)
 
     def keypoint_loss(self, poses: torch.Tensor, kps: torch.Tensor, betas=None, joint_weight=None, rows=None, sel17=None,
                       out_loss=None, out_grad=None, grad_scale: float = 1.0, accumulate: bool = False):

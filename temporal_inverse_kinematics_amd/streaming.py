@@ -17,6 +17,15 @@ the frame the step just solved and its own keypoints from the device ring), so
 also ties each refined pose to the previous refined one, the causal
 counterpart of refine.refine_smooth. Nobody has measured a good smooth_weight
 on real detections: there is no tuned default, 0 means no tie.
+
+Imperfect detections: `push(frame, conf)` takes 17 confidences. A keypoint with
+confidence 0 or a non-finite coordinate is missing: the network gets the last
+value the stream accepted for it (hold-last, a stated rule that nobody has
+measured on real detections), and the refinement weighs the frame's keypoints
+by conf * joint_weight (a missing hip: the whole frame by 0). `robust_sigma > 0`
+gives the refinement's data term the Geman-McClure scale of
+SMPLX.refine_frames; there is no tuned value, 0 is off. A plain `push(frame)`
+behaves as before, its refusal of a NaN included.
 """
 from __future__ import annotations
 
@@ -48,11 +57,36 @@ def check_refine_args(refine, smplx_model, betas, prior_weight, smooth_weight, l
     return iters, mu, smooth, lam0, b, w
 
 
+def check_stream_robust(iters: int, robust_sigma) -> float:
+    """OnlineIK's robust_sigma -> float: >= 0 and finite (smplx_fk.check_robust_args), and > 0 only on a refining
+    stream (the robust term lives in the refine launch). ValueError otherwise; the library is not asked."""
+    from .smplx_fk import check_robust_args
+    sigma, _ = check_robust_args(robust_sigma)
+    if sigma > 0.0 and iters == 0:
+        raise ValueError("robust_sigma > 0 needs refine > 0: the robust term belongs to the refinement launch")
+    return sigma
+
+
+def check_conf(conf, frames: Optional[int] = None) -> np.ndarray:
+    """The confidences of a push, (17,), or with `frames` those of a sequence, (frames,17): finite and >= 0 -> them
+    as contiguous float32. ValueError otherwise (a wrong shape, a negative value, a NaN, an Inf); the library is
+    not asked."""
+    c = np.ascontiguousarray(conf, dtype=np.float32)
+    want = (17,) if frames is None else (int(frames), 17)
+    if c.shape != want:
+        raise ValueError(f"conf must be {want} confidences (COCO order), got shape {c.shape}")
+    if not (np.isfinite(c).all() and (c >= 0).all()):
+        raise ValueError("conf must be finite and >= 0 (0 = the keypoint is missing)")
+    return c
+
+
 class OnlineIK:
     def __init__(self, model, win_size: Optional[int] = None, use_graph: bool = True, refine: int = 0, smplx_model=None,
-                 betas=None, prior_weight: float = 1e-2, smooth_weight: float = 0.0, lam0: float = 1e-2, joint_weight=None):
+                 betas=None, prior_weight: float = 1e-2, smooth_weight: float = 0.0, lam0: float = 1e-2, joint_weight=None,
+                 robust_sigma: float = 0.0):
         iters, mu, smooth, lam0, b, w = check_refine_args(refine, smplx_model, betas, prior_weight, smooth_weight, lam0,
                                                           joint_weight)
+        sigma = check_stream_robust(iters, robust_sigma)
         reg = getattr(model, "regressor", model)
         self.win_size = int(win_size if win_size is not None else model.hparams.win_size)
         self.h = self.win_size // 2
@@ -89,6 +123,14 @@ class OnlineIK:
             _lib.check(lib.tik_stream_set_refine(self._s, smplx_model._h, None if b is None else b.ctypes.data_as(_lib._F),
                                                  None if w is None else w.ctypes.data_as(_lib._F), iters, mu, smooth, lam0),
                        "OnlineIK")
+            if sigma > 0.0:
+                _lib.check(lib.tik_stream_set_robust(self._s, sigma), "OnlineIK")
+        self.robust_sigma = sigma
+        # a push with confidences: two more preallocated buffers, as for the frame
+        self._push_conf_fn = lib.tik_stream_push_conf
+        self._cbuf = np.ones(17, np.float32)
+        self._cptr = self._cbuf.ctypes.data_as(_lib._F)
+        self._last_conf = None
 
     def __del__(self):
         try:
@@ -100,6 +142,7 @@ class OnlineIK:
     def reset(self):
         _lib.check(_lib.load().tik_stream_reset(self._s))
         self._last = None
+        self._last_conf = None
         self._have_pose = False
 
     @property
@@ -111,20 +154,32 @@ class OnlineIK:
         _lib.check(_lib.load().tik_stream_raw_pose(self._s, self._raw.ctypes.data_as(_lib._F)), "OnlineIK.raw")
         return self._raw.copy()
 
-    def push(self, frame: np.ndarray) -> Optional[np.ndarray]:
+    def push(self, frame: np.ndarray, conf=None) -> Optional[np.ndarray]:
         """frame (17,3) -> the (66,) pose of the frame h pushes back (refined when refine > 0), or None while filling.
         A frame with a NaN or an Inf in it raises ValueError and is not appended: the
-        stream goes on as if it had never been offered."""
+        stream goes on as if it had never been offered.
+        conf (17,) finite and >= 0 (tik_stream_push_conf): keypoint k is missing where conf[k] is 0 or one of its
+        coordinates is not finite. The network gets the last value the stream accepted for it (hold-last; a stated
+        rule, nobody has measured it on real detections), and a refining stream weighs keypoint k of the frame by
+        conf[k] * joint_weight[k], all 17 by 0 where conf[11] or conf[12] is 0. ValueError, nothing appended: a bad
+        conf, and a missing keypoint that has not been seen since the stream was created or reset."""
         f = np.asarray(frame, dtype=np.float32)
         if f.size != 51:
             raise ValueError("expected one (17,3) COCO frame")
+        if conf is not None:
+            conf = check_conf(conf)
         self._fbuf[:] = f.reshape(-1)
-        rc = self._push_fn(self._s, self._fptr, self._pptr)
+        if conf is None:
+            rc = self._push_fn(self._s, self._fptr, self._pptr)
+        else:
+            self._cbuf[:] = conf
+            rc = self._push_conf_fn(self._s, self._fptr, self._cptr, self._pptr)
         if rc == _lib.TIK_E_INVALID:
             # a NaN or Inf in the frame: it was not appended (include/tik.h), so flush must not repeat it
             _lib.check(rc, "OnlineIK.push")
         # the last frame the ring took (flush repeats it): the two buffers change places, no copy
         self._last = self._fbuf
+        self._last_conf = None if conf is None else conf.copy()
         self._fbuf, self._obuf, self._fptr, self._optr = self._obuf, self._fbuf, self._optr, self._fptr
         if rc < 0:
             _lib.check(rc, "OnlineIK.push")
@@ -133,20 +188,23 @@ class OnlineIK:
         return self._pose.copy() if rc == 1 else None
 
     def flush(self):
-        """Poses of the last h frames (right edge padding = repeat the last frame)."""
+        """Poses of the last h frames (right edge padding = repeat the last accepted frame, with its confidences:
+        a keypoint missing in it is filled again with the value the stream holds)."""
         out = []
         for _ in range(self.h):
-            p = self.push(self._last.reshape(17, 3))
+            p = self.push(self._last.reshape(17, 3), self._last_conf)
             if p is not None:
                 out.append(p)
         return out
 
-    def run(self, seq: np.ndarray) -> np.ndarray:
-        """Whole sequence through the online path: (F,17,3) -> (F,66)."""
+    def run(self, seq: np.ndarray, conf=None) -> np.ndarray:
+        """Whole sequence through the online path: (F,17,3) -> (F,66). conf: None or (F,17), one row per push."""
+        if conf is not None:
+            conf = check_conf(conf, len(seq))
         self.reset()
         out = []
-        for fr in seq:
-            p = self.push(fr)
+        for i, fr in enumerate(seq):
+            p = self.push(fr, None if conf is None else conf[i])
             if p is not None:
                 out.append(p)
         out += self.flush()
