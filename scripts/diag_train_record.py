@@ -8,7 +8,10 @@ given dropout mask, three at (3,64) with the seeded device mask, one more at
 of every step; after each group every entry's value, gradient, exp_avg and
 exp_avg_sq, and the saved activations 0 and 2..6 of blocks 0, 2 and 7. Then
 tik_trainer_eval's poses and loss at (4,9) and (2,17), and again after a
-tik_trainer_write of a dense backbone.A.
+tik_trainer_write of a dense backbone.A. Then a second handle with the three
+synthetic body models and kp_weight 0.5 (tik_trainer_step_kp): two steps at (8,9)
+against FK keypoints of the target poses, mixed genders; the loss, both of its
+terms (last_loss_parts) and the state after them.
 
     python scripts/diag_train_record.py > record.txt
 """
@@ -22,6 +25,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from temporal_inverse_kinematics_amd import synthetic as syn  # noqa: E402
 from temporal_inverse_kinematics_amd.models import IKPoseTrainer, default_hparams  # noqa: E402
+from temporal_inverse_kinematics_amd.smplx_fk import load_smplx_models  # noqa: E402
 from temporal_inverse_kinematics_amd.trainer import GpuTrainer  # noqa: E402
 
 V = 17
@@ -56,7 +60,7 @@ def main():
         y = torch.from_numpy(rng.normal(0, 0.5, (N, frames(T)[-1][1], 66)).astype(np.float32)).cuda()
         return x, y
 
-    def state(tag, N, T):
+    def state(tag, N, T, tr=tr):
         for what in ("value", "grad", "exp_avg", "exp_avg_sq"):
             print(f"{tag} state {what} {sha(*[tr.tensor(n, what) for n, _, k in tr._names if k == 0 or what == 'value'])}")
         fr = frames(T)
@@ -91,6 +95,27 @@ def main():
     A = torch.from_numpy(rng.uniform(0.0, 0.2, (1, V, V)).astype(np.float32)).cuda()   # dense: leaves the hop <= 2 pattern
     tr.write_tensor("backbone.A", A)
     evals("G dense A")
+
+    bodies = load_smplx_models("synthetic", "cuda", batch_size=8)
+    trk = GpuTrainer(m, lr=1e-3, smplx_models=bodies, kp_weight=0.5)
+    N, T = 8, 9
+    To = frames(T)[-1][1]
+    x, y = batch(N, T)
+    gid = torch.from_numpy(rng.integers(0, 3, N).astype(np.int32))
+    betas = torch.from_numpy(rng.normal(0, 1, (N, bodies["male"].num_betas)).astype(np.float32)).cuda()
+    full = torch.zeros((N * To, 55, 3), device="cuda")
+    full[:, :22] = y.reshape(N * To, 22, 3)
+    rb = betas.repeat_interleave(To, 0).contiguous()
+    kps = torch.zeros((N * To, V, 3), device="cuda")
+    for g, name in enumerate(sorted(bodies)):
+        sel = torch.nonzero(gid.cuda().repeat_interleave(To) == g).flatten()
+        if len(sel):
+            kps[sel] = bodies[name].joints(full[sel], rb[sel].contiguous(), select="coco")
+    for i in range(2):
+        loss = trk.step(x, y, seed=40 + i, target_keypoints=kps.reshape(N, To, V, 3), betas=betas, gender_id=gid)
+        parts = trk.last_loss_parts
+        print(f"H kp (8,9) step {trk.steps} loss {sha(loss)} {float(loss)!r} parts {sha(parts)} {parts.tolist()!r}")
+    state("H kp (8,9)", N, T, trk)
     torch.cuda.synchronize()
 
 

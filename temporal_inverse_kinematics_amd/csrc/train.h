@@ -1,9 +1,12 @@
-// train.h — kernels of the training step (csrc/train.hip): train-mode
-// BatchNorm statistics and backward, the graph mix and its gradients, the
-// weight-gradient GEMM (fp32 MFMA, split over rows), im2col / zero-upsample
-// for the temporal-conv backward, the head's LeakyReLU + dropout, the MSE
-// loss and Adam. The data-parallel GEMMs of the forward and of every input
-// gradient run on the fp32 implicit-GEMM kernel (cgemm.hip).
+// train.h — kernels of the training step, in the order of their files:
+// train-mode BatchNorm statistics and backward (train_bn.hip); the graph mix
+// and its gradients, the weight-gradient GEMM (fp32 MFMA, split over rows),
+// im2col / zero-upsample for the temporal-conv backward (train_wgrad.hip);
+// the descriptor batches: weight re-layouts and the eval fold
+// (train_batch.hip); the head's LeakyReLU + dropout, the losses and Adam
+// (train_head.hip). Shared device code: train_dev.h. The data-parallel GEMMs
+// of the forward and of every input gradient run on the fp32 implicit-GEMM
+// kernel (cgemm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,8 +17,8 @@ namespace tik {
 //   G != nullptr: (sum G, sum G * (A - mean[c]))   (mean may be null -> 0)
 // rows of C floats (ld = C). Returns the chunk count through *nchunk.
 // M (optional, G mode): ReLU backward folded in, g = M > 0 ? G : 0.
-hipError_t launch_colstats(const float* A, const float* G, const float* mean, long long R, int C, double* part,
-                           int max_chunks, int* nchunk, hipStream_t st, const float* M = nullptr);
+hipError_t launch_colstats(const float* A, const float* G, const float* M, const float* mean, long long R, int C,
+                           double* part, int max_chunks, int* nchunk, hipStream_t st);
 // train-mode BatchNorm statistics from colstats(A): mean, invstd, scale =
 // gamma*invstd, shift = beta - mean*scale per column into stat[4][C]; running
 // stats updated (momentum, unbiased variance). cmap: column -> channel
@@ -35,8 +38,8 @@ hipError_t launch_affine(float* out, const float* X, const float* sc, const floa
                          const float* sc2, const float* sh2, long long R, int C, int relu, hipStream_t st);
 // out = g*k0 + (x - mean)*k1 + k2 (BatchNorm input gradient); stat = bn_fwd_finalize's stat
 // M (optional): g = M > 0 ? G : 0 (ReLU backward folded in)
-hipError_t launch_bn_bwd_apply(float* out, const float* G, const float* X, const float* stat, const float* k,
-                               long long R, int C, hipStream_t st, const float* M = nullptr);
+hipError_t launch_bn_bwd_apply(float* out, const float* G, const float* M, const float* X, const float* stat,
+                               const float* k, long long R, int C, hipStream_t st);
 // out = M > 0 ? G : 0 (ReLU backward on its output); n elements
 hipError_t launch_relu_bwd(float* out, const float* G, const float* M, long long n, hipStream_t st);
 // out[f][w][c] = sum_v Amat(v, w) in[f][v][c]; Amat = A (trans=0) or A^T (trans=1), V = 17
@@ -68,6 +71,7 @@ struct PermDesc {
     int d0, d1, d2;
     long long ds0, ds1, ds2, soff, ss0, ss1, ss2;
     long long block0;   // first workgroup (permute_batch_blocks)
+    __host__ __device__ long long count() const { return (long long)d0 * d1 * d2; }
 };
 // assigns block ranges; returns the grid size
 long long permute_batch_blocks(PermDesc* descs, int nd);
@@ -84,7 +88,7 @@ hipError_t launch_leaky_dropout_bwd(float* dP, const float* dD, const float* P, 
 hipError_t launch_mse(const float* O, int ldo, const float* T, long long rows, int cols, float* dO, float* loss,
                       hipStream_t st);
 // The keypoint term of the loss from the per-frame losses lf (rows; 1/2 sum_k w_k |r_k|^2 each, zero where no body
-// model has the row): kp_mse = 2 sum(lf) / (51 rows), summed in double in a fixed order as launch_mse sums.
+// model has the row): kp_mse = 2 sum(lf) / (51 rows), summed in double by launch_mse's reduction.
 // loss[0] = pose_mse[0] + weight kp_mse (pose_mse[0] alone at weight 0; loss may be pose_mse);
 // parts (or null) = {pose_mse[0], kp_mse}
 hipError_t launch_kp_loss_reduce(const float* lf, long long rows, float weight, const float* pose_mse, float* loss,
@@ -109,6 +113,7 @@ struct FoldDesc {
     BnRef bn, bn2;
     const int* cmap;
     long long block0;   // first workgroup (fold_batch_blocks)
+    __host__ __device__ long long count() const { return (long long)rows * cols; }
 };
 // assigns block ranges; returns the grid size
 long long fold_batch_blocks(FoldDesc* descs, int nd);

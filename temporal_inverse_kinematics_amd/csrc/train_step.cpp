@@ -13,8 +13,10 @@
 // parameters (temporal taps innermost for the forward, transposed /
 // tap-flipped for the input gradients, A_eff = A * edge_importance). GEMMs
 // (forward convs, input gradients) run on the fp32 implicit-GEMM kernel
-// (cgemm.hip); weight gradients on train.hip's row-split MFMA kernel;
-// BatchNorm, graph mix, activation and loss kernels in train.hip.
+// (cgemm.hip); weight gradients on train_wgrad.hip's row-split MFMA kernel
+// beside the graph mix; BatchNorm and activation kernels in train_bn.hip,
+// the head, losses and Adam in train_head.hip, the re-layouts in
+// train_batch.hip (interface: train.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -125,7 +127,8 @@ int gemm_splitk(tik_trainer* t, tik::CgemmArgs a, hipStream_t st) {
 int bn_stats(tik_trainer* t, const float* X, long long R, int C, const int* cmap, long long g, long long b,
              long long rm, long long rv, float* stat, hipStream_t st) {
     int nc = 0;
-    HIP_TRY(tik::launch_colstats(X, nullptr, nullptr, R, C, t->partd.p, (int)(t->partd_cap / (2LL * C)), &nc, st));
+    HIP_TRY(tik::launch_colstats(X, nullptr, nullptr, nullptr, R, C, t->partd.p, (int)(t->partd_cap / (2LL * C)), &nc,
+                                 st));
     HIP_TRY(tik::launch_bn_fwd_finalize(t->partd.p, nc, R, C, cmap, t->P.p + g, t->P.p + b, t->B.p + rm, t->B.p + rv,
                                         t->momentum, BN_EPS, stat, st));
     return TIK_OK;
@@ -136,16 +139,17 @@ int bn_stats(tik_trainer* t, const float* X, long long R, int C, const int* cmap
 int bn_back(tik_trainer* t, const float* Gr, const float* X, long long R, int C, const int* cmap, long long g,
             long long b, const float* stat, float* out, hipStream_t st, const float* Mr = nullptr) {
     int nc = 0;
-    HIP_TRY(tik::launch_colstats(X, Gr, stat, R, C, t->partd.p, (int)(t->partd_cap / (2LL * C)), &nc, st, Mr));
+    HIP_TRY(tik::launch_colstats(X, Gr, Mr, stat, R, C, t->partd.p, (int)(t->partd_cap / (2LL * C)), &nc, st));
     HIP_TRY(tik::launch_bn_bwd_finalize(t->partd.p, nc, R, C, cmap, t->P.p + g, stat, t->G.p + g, t->G.p + b,
                                         t->k.p, st));
-    if (out) HIP_TRY(tik::launch_bn_bwd_apply(out, Gr, X, stat, t->k.p, R, C, st, Mr));
+    if (out) HIP_TRY(tik::launch_bn_bwd_apply(out, Gr, Mr, X, stat, t->k.p, R, C, st));
     return TIK_OK;
 }
 
 int colsum(tik_trainer* t, const float* X, long long R, int C, float* dst, hipStream_t st) {
     int nc = 0;
-    HIP_TRY(tik::launch_colstats(X, nullptr, nullptr, R, C, t->partd.p, (int)(t->partd_cap / (2LL * C)), &nc, st));
+    HIP_TRY(tik::launch_colstats(X, nullptr, nullptr, nullptr, R, C, t->partd.p, (int)(t->partd_cap / (2LL * C)), &nc,
+                                 st));
     HIP_TRY(tik::launch_colsum_finalize(t->partd.p, nc, C, dst, st));
     return TIK_OK;
 }
