@@ -1,7 +1,7 @@
 """Config #4: SMPL-X full 55-joint FK + 10475-vertex LBS, batch=4096, 1 GPU.
 
     python bench_fk.py [--batch 4096] [--steps 10] [--warmup 20] [--joints {all,coco}] [--jacobian] [--refine] [--refine-fused]
-                       [--robust S] [--shape-jacobian] [--fit-shape] [--smooth]
+                       [--robust S] [--shape-jacobian] [--fit-shape] [--smooth] [--metrics]
 
 Prints one JSON line: bodies/s, and per kernel (HIP events around every launch
 of a second pass of the same steps, tik_fk_profile) the algorithmic TFLOP/s of
@@ -20,7 +20,9 @@ refine.fit_shape of `batch` frames, and tik_lm_accumulate + tik_lm_solve_sum
 alone), both at the same batch. --smooth adds a "smooth" key: tik_lm_solve_chain
 at (m,n) = (51,66) for one sequence of 256 and of 4096 frames and for 64
 sequences of 64 frames, the per-frame tik_lm_solve at the same frame counts, and
-one iteration of refine.refine_smooth.
+one iteration of refine.refine_smooth. --metrics adds a "metrics" key:
+SMPLX.pose_metrics (one launch) beside the composed path (SMPLX.joints, torch ops and
+a batched 3x3 torch.linalg.svd) and SMPLX.keypoint_loss at loss only (the same FK).
 """
 import argparse, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -275,6 +277,65 @@ def measure_refine_fused(batch=4096, steps=10, warmup=20, iters=3, robust=0.0):
                      "allocated per call"}
 
 
+def composed_metrics(m, full, kps):
+    """mpjpe and pa_mpjpe (B,) of the composed path: SMPLX.joints, then Umeyama's alignment in torch ops with a batched
+    3x3 torch.linalg.svd (unit weights, the proper rotation)."""
+    import torch
+    x = m.joints(full, select="coco")
+    x = x - 0.5 * (x[:, 11:12] + x[:, 12:13])
+    y = kps - 0.5 * (kps[:, 11:12] + kps[:, 12:13])
+    mpjpe = (x - y).norm(dim=2).mean(dim=1)
+    xc, yc = x - x.mean(dim=1, keepdim=True), y - y.mean(dim=1, keepdim=True)
+    U, D, Vt = torch.linalg.svd(yc.transpose(1, 2) @ xc)
+    sgn = torch.sign(torch.linalg.det(U) * torch.linalg.det(Vt))
+    S = torch.ones_like(D)
+    S[:, 2] = sgn
+    Rm = (U * S[:, None, :]) @ Vt
+    sc = (D * S).sum(dim=1) / (xc * xc).sum(dim=(1, 2))
+    pa = (sc[:, None, None] * (xc @ Rm.transpose(1, 2)) - yc).norm(dim=2).mean(dim=1)
+    return mpjpe, pa
+
+
+def measure_metrics(batch=4096, steps=10, warmup=20):
+    """SMPLX.pose_metrics at `batch` frames on resident tensors (one launch, outputs preallocated), the composed path
+    on the same frames (composed_metrics above), and SMPLX.keypoint_loss at loss only through the C entry point: the
+    same FK without the alignment. Also the largest difference between the two paths' values."""
+    import torch
+    from temporal_inverse_kinematics_amd import _build, _lib, synthetic as syn
+    from temporal_inverse_kinematics_amd.smplx_fk import SMPLX
+    _build.build()
+    m = SMPLX(syn.synthetic_smplx_constants(seed=1), batch_size=batch)
+    pose, _ = syn.synthetic_fk_inputs(batch, seed=1)
+    full = torch.zeros((batch, 55, 3), device="cuda")
+    full[:, :22] = torch.from_numpy(pose[:, :22]).cuda()
+    target = (full[:, :22] + 0.05).reshape(batch, 66).contiguous()
+    tfull = torch.zeros_like(full)
+    tfull[:, :22] = target.reshape(batch, 22, 3)
+    kps = m.joints(tfull, select="coco")
+    th = full[:, :22].reshape(batch, 66).contiguous()
+    out, oj = torch.empty((batch, 4), device="cuda"), torch.empty((batch, 17, 3), device="cuda")
+    tk, rk = _timed(lambda: m.pose_metrics(th, kps, target_poses=target, out=out), steps, warmup)
+    tj, rj = _timed(lambda: m.pose_metrics(th, kps, target_poses=target, out=out, out_joints=oj), steps, warmup)
+    tc, rc = _timed(lambda: composed_metrics(m, full, kps), steps, warmup)
+    loss = torch.empty((batch,), device="cuda")
+    lib, st = _lib.load(), _lib.stream_of(th)
+    kploss = lambda: _lib.check(lib.tik_fk_keypoint_loss(m._h, th.data_ptr(), 66, kps.data_ptr(), None, 0, None, 0, None, None,
+                                                         batch, loss.data_ptr(), None, 0, 1.0, 0, st))
+    tl, rl = _timed(kploss, steps, warmup)
+    got = m.pose_metrics(th, kps, target_poses=target, out=out)
+    cm, cp = composed_metrics(m, full, kps)
+    return {"batch": batch, "steps": steps, "warmup": warmup, "pose_metrics_ms": round(tk, 4),
+            "pose_metrics_with_joints_ms": round(tj, 4), "composed_ms": round(tc, 4), "keypoint_loss_only_ms": round(tl, 4),
+            "composed_over_kernel": round(tc / tk, 2), "pose_metrics_ms_rounds": rk, "pose_metrics_with_joints_ms_rounds": rj,
+            "composed_ms_rounds": rc, "keypoint_loss_only_ms_rounds": rl,
+            "max_abs_diff_mpjpe": float((got["mpjpe"] - cm).abs().max()), "max_abs_diff_pa_mpjpe": float((got["pa_mpjpe"] - cp).abs().max()),
+            "mean_mpjpe": float(got["mpjpe"].mean()), "mean_pa_mpjpe": float(got["pa_mpjpe"].mean()),
+            "mean_mpjae": float(got["mpjae"].mean()),
+            "basis": "median of 5 rounds of `steps` calls between HIP events, resident tensors; pose_metrics: one launch, "
+                     "outputs preallocated; composed: SMPLX.joints + torch ops + batched 3x3 torch.linalg.svd, outputs "
+                     "allocated per call; keypoint_loss_only: tik_fk_keypoint_loss with grad = NULL"}
+
+
 def measure_shape_jacobian(batch=4096, steps=10, warmup=20):
     """SMPLX.joints_shape_jacobian(select="coco", return_joints=False) at `batch` bodies
     on a fresh handle, measured like measure_jacobian: call time, the per-launch
@@ -404,6 +465,9 @@ def main():
     ap.add_argument("--smooth", action="store_true",
                     help="also time tik_lm_solve_chain (1 x 256, 1 x 4096 and 64 x 64 frames) beside tik_lm_solve, and one "
                          "refine.refine_smooth iteration")
+    ap.add_argument("--metrics", action="store_true",
+                    help="also time SMPLX.pose_metrics beside the composed path (SMPLX.joints + torch.linalg.svd) and "
+                         "SMPLX.keypoint_loss at loss only")
     a = ap.parse_args()
     from temporal_inverse_kinematics_amd import synthetic as syn
     out = measure_fk(a.batch, a.steps, a.warmup)
@@ -421,6 +485,8 @@ def main():
         out["fit_shape"] = measure_fit_shape(a.batch, a.steps, a.warmup)
     if a.smooth:
         out["smooth"] = measure_smooth(a.steps, a.warmup)
+    if a.metrics:
+        out["metrics"] = measure_metrics(a.batch, a.steps, a.warmup)
     from oracle import smplx_lbs as sl
     c = syn.synthetic_smplx_constants(seed=1)
     pose, betas = syn.synthetic_fk_inputs(16, seed=1)

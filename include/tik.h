@@ -692,6 +692,45 @@ int tik_fk_keypoint_loss(tik_fk_t fk, const float* poses, int poses_ld, const fl
                          const float* joint_w, int joint_w_ld, const int* sel17, const int* rows, int B, float* loss,
                          float* grad, int grad_ld, float grad_scale, int accumulate, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The pose metrics of B frames in one launch (what a pose regressor is
+ * judged by): one workgroup per frame, tik_fk_keypoint_loss's FK, then the
+ * alignment in one wave's registers. Per frame f, k < 17 keypoints:
+ *   x_k = rel(FK keypoints(theta_f, betas_f)), y_k = rel(kps_f), W = sum_k w_k, n = #{k : w_k > 0}
+ *   out[f][0] mpjpe    = sum_k w_k |x_k - y_k| / W                      (metres; NaN when W = 0)
+ *   out[f][1] pa_mpjpe = sum_k w_k |s R (x_k - mx) - (y_k - my)| / W    (NaN when n < 3)
+ *   out[f][2] mpjae    = (1/22) sum_{j<22} angle(R_j^T R*_j)            (radians; NaN when target_poses == NULL)
+ *   out[f][3] weight   = W
+ * mx, my are the w-weighted means; R in SO(3) is the proper rotation that
+ * minimises sum w |s R (x - mx) - (y - my)|^2 (Horn's quaternion form: a
+ * mirrored body is not aligned by a reflection, and a planar set of keypoints
+ * needs no special case), s = sum w (y - my) . R (x - mx) / sum w |x - mx|^2.
+ * R_j = the rotation of theta_j + pose_mean_j, R*_j that of target_poses;
+ * angle = atan2(|axial(D)|, (tr D - 1) / 2), sound at 0 and at pi.
+ * poses: row f at poses + f poses_ld (poses_ld >= 66); target_poses: row f at
+ * target_poses + f target_ld (target_ld >= 66), or NULL; kps (.,17,3); betas,
+ * betas_ld, joint_w, joint_w_ld, sel17 and rows exactly as in
+ * tik_fk_keypoint_loss (rows is NOT range-checked on the device). flags:
+ * TIK_REFINE_SKIP_NONFINITE as in tik_fk_refine_robust: a keypoint with a NaN
+ * or Inf component weighs 0, and a frame without column 11 or 12 has W = 0.
+ * out (.,4) indexed by frame; joints_out (.,17,3) indexed by frame, or NULL:
+ * the x_k. All device fp32 but sel17 (host). A pose value that is not finite
+ * gives its frame NaN in all four columns; without the flag a NaN keypoint
+ * gives NaN in columns 0 and 1; no other frame is affected. fp32 in a fixed
+ * order (a fixed number of Jacobi sweeps, no loop until converged), no
+ * atomics, one writer per output element: a frame's bits do not depend on B,
+ * on its place in the batch or on rows. Both skinning table forms of the
+ * handle. No workspace, nothing uploaded, stream-ordered.
+ * TIK_E_INVALID, before any device work: null fk / poses / kps / out, B <= 0,
+ * poses_ld < 66, target_ld < 66 with target_poses, betas_ld not 0 or >= nb,
+ * joint_w_ld not 0 or 17, a bit of flags other than the one defined, a joint
+ * index out of range, a landmark of three vertices or a contour landmark in
+ * sel17.
+ * ---------------------------------------------------------------------- */
+int tik_fk_pose_metrics(tik_fk_t fk, const float* poses, int poses_ld, const float* kps, const float* betas, int betas_ld,
+                        const float* joint_w, int joint_w_ld, const float* target_poses, int target_ld, const int* sel17,
+                        const int* rows, int B, int flags, float* out, float* joints_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,7 @@ SIGNATURES: Dict[str, Tuple[object, Tuple]] = {
                                   ctypes.c_float, _I, _P, _P, _P, _P, ctypes.c_float, _I, _P, _P)),
     "tik_fk_keypoint_loss": (_I, (_P, _P, _I, _P, _P, _I, _P, _I, ctypes.POINTER(_I), _P, _I, _P, _P, _I, ctypes.c_float, _I,
                                   _P)),
+    "tik_fk_pose_metrics": (_I, (_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, ctypes.POINTER(_I), _P, _I, _I, _P, _P, _P)),
     "tik_fk_workspace_bytes": (ctypes.c_longlong, (_P,)),
     "tik_fk_profile": (_I, (_P, _I)),
     "tik_fk_profile_count": (_I, (_P,)),

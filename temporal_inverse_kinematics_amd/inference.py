@@ -7,7 +7,7 @@ reference, each window's output frame 0 is the solution for frame idx
 CLI (README.md:24-26):
     python -m temporal_inverse_kinematics_amd.inference <moveai_3d.npz> [SMPLX_DIR]
         [--ckpt model.ckpt] [--win-size 64] [--out poses.npy] [--check] [--refine N]
-        [--fit-shape R] [--smooth W] [--robust S]
+        [--fit-shape R] [--smooth W] [--robust S] [--metrics]
 Without --ckpt the seeded synthetic weights are used (the trained checkpoint
 is not distributed with the reference: .MISSING_LARGE_BLOBS:2).
 """
@@ -70,9 +70,73 @@ def fk_check(poses, seq_3d_kps, smplx_model, betas=None) -> dict:
     return {"per_joint": per_joint, "mpjpe": mpjpe, "mean": float(mpjpe.mean())}
 
 
+def _nanmean(v: np.ndarray) -> float:
+    """The mean over the finite entries; NaN where there is none (the mean over nothing)."""
+    ok = np.isfinite(v)
+    return float(v[ok].mean()) if ok.any() else float("nan")
+
+
+def evaluate_poses(poses, seq_3d_kps, smplx_model, betas=None, target_poses=None, joint_weight=None,
+                   seq_starts=None) -> dict:
+    """The metrics a pose regressor is judged by, per frame, on the device
+    (SMPLX.pose_metrics, one launch per run of MAX_WINDOWS_PER_CALL frames): poses
+    (F,66), seq_3d_kps (F,17,3) COCO, both made root-relative as in fk_check.
+    -> {"mpjpe", "pa_mpjpe", "mpjae", "weight", "accel": (F,) host arrays, and
+    "mpjpe_mean", "pa_mpjpe_mean", "mpjae_mean", "accel_mean": their means over the
+    frames that have a value (NaN where none has)}. mpjpe and pa_mpjpe in metres
+    (pa_mpjpe after the best similarity transform with a proper rotation), mpjae
+    in radians against target_poses (F,66) (NaN without them). accel: the
+    acceleration error mean_k |(x_{f+1} - 2 x_f + x_{f-1}) - (y_{f+1} - 2 y_f + y_{f-1})|
+    of the FK keypoints x and the keypoints y, for the interior frames of each
+    sequence (NaN on a sequence's first and last frame); seq_starts: None (one
+    sequence) or S+1 frame indices (smplx_fk.lm_chain_starts). betas: None,
+    (nb,) or (F,nb); joint_weight: None, (17,) or (F,17) non-negative. A
+    non-finite keypoint counts as missing (weight 0); a frame without both hips
+    has weight 0 and no mpjpe."""
+    from .refine import _check_joint_weight, _chunks, _rows, _upload
+    from .smplx_fk import lm_chain_starts
+    F = int(np.asarray(poses).shape[0])
+    starts = lm_chain_starts(F, seq_starts)
+    w = _check_joint_weight(joint_weight, F)
+    b = None if betas is None else np.asarray(betas, np.float32)
+    if b is not None and b.ndim == 2 and b.shape[0] != F:
+        raise ValueError(f"betas must be (nb,) or ({F}, nb), got {b.shape}")
+    th, _, kps, _ = _upload(smplx_model, poses, seq_3d_kps)
+    dev = th.device
+    nb = smplx_model.num_betas
+    beta = None if b is None else torch.as_tensor(np.ascontiguousarray(b[..., :nb]), device=dev)
+    tgt = None
+    if target_poses is not None:
+        t = np.asarray(target_poses, dtype=np.float32)
+        if t.ndim != 2 or t.shape[0] != F or t.shape[1] < 66:
+            raise ValueError(f"target_poses must be ({F}, >= 66), got {t.shape}")
+        tgt = torch.as_tensor(np.ascontiguousarray(t[:, :66]), device=dev)
+    wd = None if w is None else torch.as_tensor(w, device=dev)
+    out = torch.empty((F, 4), device=dev, dtype=torch.float32)
+    x = torch.empty((F, 17, 3), device=dev, dtype=torch.float32)
+    with torch.no_grad():
+        for s, n in _chunks(F):
+            smplx_model.pose_metrics(_rows(th, s, n), _rows(kps, s, n),
+                                     betas=beta if beta is None or beta.dim() == 1 else _rows(beta, s, n),
+                                     joint_weight=wd if wd is None or wd.dim() == 1 else _rows(wd, s, n),
+                                     target_poses=_rows(tgt, s, n), skip_nonfinite=True, out=out[s:s + n],
+                                     out_joints=x[s:s + n])
+        accel = torch.full((F,), float("nan"), device=dev)
+        e = x - (kps - 0.5 * (kps[:, 11:12] + kps[:, 12:13]))
+        for q in range(len(starts) - 1):
+            a, z = int(starts[q]), int(starts[q + 1])
+            if z - a >= 3:
+                accel[a + 1:z - 1] = (e[a + 2:z] - 2.0 * e[a + 1:z - 1] + e[a:z - 2]).norm(dim=2).mean(dim=1)
+    h = out.cpu().numpy()
+    res = {"mpjpe": h[:, 0], "pa_mpjpe": h[:, 1], "mpjae": h[:, 2], "weight": h[:, 3], "accel": accel.cpu().numpy()}
+    for k in ("mpjpe", "pa_mpjpe", "mpjae", "accel"):
+        res[k + "_mean"] = _nanmean(res[k])
+    return res
+
+
 def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = None, win_size: int = 64,
              device="cuda", check: bool = False, refine: int = 0, fit_shape: int = 0, smooth: float = 0.0,
-             robust: float = 0.0):
+             robust: float = 0.0, metrics: bool = False):
     """inference.run_test:110-145: moveai npz -> COCO -> IK -> (optional) SMPL-X FK.
     check=True (with an SMPL-X dir): the result gains "fk_check" (fk_check above).
     refine=N > 0 (with an SMPL-X dir): N Levenberg-Marquardt iterations on the
@@ -90,7 +154,10 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
     robust=S > 0 (with an SMPL-X dir and refine=N > 0, without fit_shape and
     smooth): the N iterations run in the fused kernel (refine_poses(fused=True))
     with the Geman-McClure scale S in metres and non-finite keypoints treated
-    as missing. There is no tuned S; robust=0 leaves every output as it is."""
+    as missing. There is no tuned S; robust=0 leaves every output as it is.
+    metrics=True (with an SMPL-X dir): the result gains "metrics"
+    (evaluate_poses of the solved poses against the keypoints) and, where poses
+    were refined, "metrics_refined". metrics=False leaves every output as it is."""
     if refine < 0:
         raise ValueError(f"refine must be >= 0, got {refine}")
     if fit_shape < 0:
@@ -108,6 +175,8 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
     if robust and (not (smplx_dir and refine > 0) or fit_shape or smooth):
         raise ValueError("robust needs an SMPL-X dir (or 'synthetic') and refine=N > 0, and neither fit_shape nor smooth: "
                          "the robust term lives in the fused kernel, not in the launched loops")
+    if metrics and not smplx_dir:
+        raise ValueError("metrics needs an SMPL-X dir (or 'synthetic'): the metrics run the FK")
     d = np.load(npz_path, allow_pickle=False)
     # the moveai_3d -> COCO conversion on the device (one gather kernel, bit-identical to the host form)
     seq = kp.moveai3d_to_coco_device(torch.as_tensor(np.ascontiguousarray(d["joints_3d"], dtype=np.float32),
@@ -148,6 +217,11 @@ def run_test(npz_path: str, smplx_dir: str | None = None, ckpt: str | None = Non
                 result["poses_refined"] = refine_poses(poses, result["coco"], models["male"], iters=refine)["poses"]
             if check:
                 result["fk_check_refined"] = fk_check(result["poses_refined"], result["coco"], models["male"])
+        if metrics:
+            result["metrics"] = evaluate_poses(poses, result["coco"], models["male"])
+            if "poses_refined" in result:
+                result["metrics_refined"] = evaluate_poses(result["poses_refined"], result["coco"], models["male"],
+                                                           betas=result.get("betas"))
     return result
 
 
@@ -172,6 +246,9 @@ def build_parser():
     p.add_argument("--robust", type=float, default=0.0, metavar="S",
                    help="with SMPLX_DIR and --refine N (without --fit-shape and --smooth): the iterations run in the fused "
                         "kernel with a Geman-McClure data term of scale S metres, and non-finite keypoints count as missing")
+    p.add_argument("--metrics", action="store_true",
+                   help="with SMPLX_DIR: print mpjpe, pa_mpjpe (metres) and the acceleration error of the solved poses "
+                        "against the input keypoints, and with --refine N those of the refined poses")
     return p
 
 
@@ -191,8 +268,10 @@ def main(argv=None):
         p.error("--smooth W needs W >= 0, an SMPLX_DIR and --refine N with N > 0 (the pose iterations it smooths)")
     if not (a.robust >= 0 and a.robust < float("inf")) or (a.robust and (not (a.smplx_dir and a.refine > 0) or a.fit_shape or a.smooth)):
         p.error("--robust S needs S >= 0, an SMPLX_DIR and --refine N with N > 0, and neither --fit-shape nor --smooth")
+    if a.metrics and not a.smplx_dir:
+        p.error("--metrics needs an SMPLX_DIR")
     r = run_test(a.npz, a.smplx_dir, a.ckpt, a.win_size, check=a.check, refine=a.refine, fit_shape=a.fit_shape,
-                 smooth=a.smooth, robust=a.robust)
+                 smooth=a.smooth, robust=a.robust, metrics=a.metrics)
     if a.out:
         np.save(a.out, r.get("poses_refined", r["poses"]))
         if "betas" in r:
@@ -207,6 +286,11 @@ def main(argv=None):
         print(f"fitted {r['betas'].shape[0]} betas in {a.fit_shape} rounds: {np.array2string(r['betas'], precision=3)}")
     if "fk_check_refined" in r:
         print(f"FK check: before {r['fk_check']['mean']:.6f} -> after {r['fk_check_refined']['mean']:.6f}")
+    for key, what in (("metrics", "solved"), ("metrics_refined", "refined")):
+        if key in r:
+            m = r[key]
+            print(f"metrics of the {what} poses: mpjpe {m['mpjpe_mean']:.6f} pa_mpjpe {m['pa_mpjpe_mean']:.6f} "
+                  f"accel {m['accel_mean']:.6f}")
     return 0
 
 

@@ -334,6 +334,38 @@ def check_kp_loss_tensors(num_betas, poses, kps, betas, joint_weight, rows, out_
             REFINE_KPS if joint_weight is not None and joint_weight.dim() == 2 else 0)
 
 
+def check_pose_metrics_tensors(num_betas, poses, kps, betas, joint_weight, target_poses, rows, out, out_joints):
+    """Shapes, dtypes and strides of SMPLX.pose_metrics's tensors -> (B, poses_ld, betas_ld, joint_w_ld, target_ld).
+    ValueError (TypeError for an argument that is no tensor); neither the library nor the device is touched."""
+    for name, t in (("poses", poses), ("kps", kps)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    for name, t in (("betas", betas), ("joint_weight", joint_weight), ("target_poses", target_poses), ("rows", rows),
+                    ("out", out), ("out_joints", out_joints)):
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor or None, got {type(t).__name__}")
+    if poses.dim() != 2 or poses.shape[0] < 1:
+        raise ValueError(f"poses must be (B >= 1, {REFINE_DOF}), got {tuple(poses.shape)}")
+    B = int(poses.shape[0])
+    poses_ld = _check_rows66("poses", poses, B)
+    target_ld = _check_rows66("target_poses", target_poses, B) if target_poses is not None else 0
+    if tuple(kps.shape) != (B, REFINE_KPS, 3):
+        raise ValueError(f"kps must be {(B, REFINE_KPS, 3)}, got {tuple(kps.shape)}")
+    if betas is not None and tuple(betas.shape) not in ((num_betas,), (B, num_betas)):
+        raise ValueError(f"betas must be {(num_betas,)} or {(B, num_betas)}, got {tuple(betas.shape)}")
+    if joint_weight is not None and tuple(joint_weight.shape) not in ((REFINE_KPS,), (B, REFINE_KPS)):
+        raise ValueError(f"joint_weight must be {(REFINE_KPS,)} or {(B, REFINE_KPS)}, got {tuple(joint_weight.shape)}")
+    _check_f32(kps=kps, betas=betas, joint_weight=joint_weight, out=out, out_joints=out_joints)
+    if out is not None and tuple(out.shape) != (B, 4):
+        raise ValueError(f"out must be {(B, 4)}, got {tuple(out.shape)}")
+    if out_joints is not None and tuple(out_joints.shape) != (B, REFINE_KPS, 3):
+        raise ValueError(f"out_joints must be {(B, REFINE_KPS, 3)}, got {tuple(out_joints.shape)}")
+    if rows is not None and (rows.dim() != 1 or rows.dtype != torch.int32 or not rows.is_contiguous() or rows.numel() > B):
+        raise ValueError(f"rows must be a contiguous int32 (n <= {B},) tensor, got {rows.dtype} {tuple(rows.shape)}")
+    return (B, poses_ld, num_betas if betas is not None and betas.dim() == 2 else 0,
+            REFINE_KPS if joint_weight is not None and joint_weight.dim() == 2 else 0, target_ld)
+
+
 def lm_chain_starts(F: int, seq_starts=None) -> np.ndarray:
     """The sequence boundaries lm_solve_chain takes: int32 (S+1,), sequence q the
     frames seq_starts[q] .. seq_starts[q+1] - 1. None: one sequence, [0, F].
@@ -680,6 +712,59 @@ class SMPLX:
                                                     grad.data_ptr(), max(int(grad.stride(0)), REFINE_DOF), float(grad_scale), int(bool(accumulate)),
                                                     _lib.stream_of(poses)), "SMPLX.keypoint_loss")
         return loss, grad
+
+    def pose_metrics(self, poses: torch.Tensor, kps: torch.Tensor, betas=None, joint_weight=None, target_poses=None,
+                     rows=None, skip_nonfinite: bool = False, out=None, out_joints=None):
+        """The pose metrics of B frames in one launch (tik_fk_pose_metrics, one
+        workgroup per frame): poses (B,66), kps (B,17,3) -> {"mpjpe", "pa_mpjpe",
+        "mpjae", "weight"}, each (B,) and a view of one (B,4) device tensor (`out`,
+        or a new one). With x = rel(FK keypoints(poses[f])), y = rel(kps[f]), w the
+        frame's weights and W their sum:
+        mpjpe = sum_k w_k |x_k - y_k| / W (metres; NaN when W = 0);
+        pa_mpjpe the same after the best similarity transform of x onto y (the
+        w-weighted means, a proper rotation, a scale; NaN with fewer than 3
+        keypoints of positive weight);
+        mpjae the mean over joints 0..21 of the angle between the rotation of
+        poses[f] and that of target_poses[f] (radians; NaN without target_poses);
+        weight = W. out_joints (B,17,3): also filled with x and returned as
+        "joints" (what evaluate_poses takes the acceleration error from).
+        betas (nb,) or (B,nb) or None (the mean shape), joint_weight (17,) or (B,17)
+        non-negative or None (ones); poses and target_poses may be row-strided
+        views (stride(0) >= 66, stride(1) == 1), everything else contiguous
+        float32 on the device. skip_nonfinite=True: a keypoint with a NaN or Inf
+        component is missing (weight 0), and a frame without column 11 or 12 has
+        W = 0; off, such a frame has NaN in mpjpe and pa_mpjpe. A pose that is not
+        finite gives its frame NaN in all four. rows: int32 (n,) device tensor of
+        distinct frame indices in [0, B) as in keypoint_loss: only those frames
+        are read and written. A frame's bits do not depend on B, on its place in
+        the batch or on rows.
+        ValueError / TypeError before the library is asked: a wrong shape, dtype,
+        stride or type."""
+        B, poses_ld, betas_ld, jw_ld, target_ld = check_pose_metrics_tensors(self.num_betas, poses, kps, betas, joint_weight,
+                                                                             target_poses, rows, out, out_joints)
+        _lib.require_gpu(kps, betas, joint_weight, out, out_joints)
+        for t in (poses, target_poses, rows):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("temporal_inverse_kinematics_amd ops run on the GPU only (got a CPU tensor)")
+        n = B
+        if rows is not None:
+            n = int(rows.numel())
+            rh = rows.detach().cpu().numpy()
+            if n and (rh.min() < 0 or rh.max() >= B or len(np.unique(rh)) != n):
+                raise ValueError(f"rows must be distinct frame indices in [0, {B})")
+        if out is None:
+            out = torch.full((B, 4), float("nan"), device=poses.device, dtype=torch.float32) if rows is not None else \
+                torch.empty((B, 4), device=poses.device, dtype=torch.float32)
+        if n:
+            _lib.check(_lib.load().tik_fk_pose_metrics(self._h, poses.data_ptr(), poses_ld, kps.data_ptr(), _lib.ptr(betas),
+                                                       betas_ld, _lib.ptr(joint_weight), jw_ld, _lib.ptr(target_poses),
+                                                       target_ld, None, _lib.ptr(rows), n,
+                                                       REFINE_SKIP_NONFINITE if skip_nonfinite else 0, out.data_ptr(),
+                                                       _lib.ptr(out_joints), _lib.stream_of(poses)), "SMPLX.pose_metrics")
+        res = {"mpjpe": out[:, 0], "pa_mpjpe": out[:, 1], "mpjae": out[:, 2], "weight": out[:, 3]}
+        if out_joints is not None:
+            res["joints"] = out_joints
+        return res
 
     def keypoint_loss_fn(self, kps: torch.Tensor, betas=None, joint_weight=None):
         """-> fn(poses (B,66)) = the per-frame keypoint loss (B,) of keypoint_loss,

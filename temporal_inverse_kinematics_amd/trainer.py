@@ -46,6 +46,7 @@ from .models import IKPoseTrainer, PoseRegressor, _Handle, _state_numpy
 _WHAT = {"value": 0, "grad": 1, "exp_avg": 2, "exp_avg_sq": 3}
 _CKPT_NAME = re.compile(r"^checkpoint_epoch=(\d+)-val_loss=(-?\d+\.\d\d|nan|inf)\.ckpt$")
 KP_POSE_DIM, KP_JOINTS = 66, 17   # include/tik.h, tik_trainer_step_kp
+VAL_METRICS = ("mpjpe", "pa_mpjpe", "mpjae")   # validation_step's extra keys with val_metrics (SMPLX.pose_metrics)
 
 
 def check_kp_args(kp_weight, n_models: int, pose_dim: int = KP_POSE_DIM, N=None, To=None, num_betas=None,
@@ -106,18 +107,23 @@ class GpuTrainer:
     """
 
     def __init__(self, model, lr: Optional[float] = None, device="cuda", smplx_models=None, kp_weight: float = 0.0,
-                 kp_joint_weight=None):
+                 kp_joint_weight=None, val_metrics: bool = False):
         """smplx_models ({gender: SMPLX}, at most 3) switches the keypoint term on: the step
         becomes tik_trainer_step_kp, loss = pose_mse + kp_weight * kp_mse with kp_mse the
         nn.MSELoss of rel(FK(predicted poses)) against rel(batch["target_keypoints_3d"]),
         back-propagated through FK. kp_weight = 0 only monitors kp_mse (the update keeps the
-        bits of the plain step). kp_joint_weight: 17 non-negative keypoint weights or None."""
+        bits of the plain step). kp_joint_weight: 17 non-negative keypoint weights or None.
+        val_metrics=True (needs smplx_models): validation_step also reports mpjpe, pa_mpjpe
+        and mpjae (pose_metrics below); off, every dict is what it is without the option."""
         reg = model.regressor if isinstance(model, IKPoseTrainer) else model
         if not isinstance(reg, PoseRegressor):
             raise TypeError("GpuTrainer expects an IKPoseTrainer or PoseRegressor")
         self.smplx_models = dict(smplx_models) if smplx_models else None
         self._genders = sorted(self.smplx_models) if self.smplx_models else []
         self.kp_weight = check_kp_args(kp_weight, len(self._genders), reg.pose_dim, kp_joint_weight=kp_joint_weight)
+        self.val_metrics = bool(val_metrics)
+        if self.val_metrics and not self.smplx_models:
+            raise ValueError("val_metrics=True needs smplx_models: the metrics run FK on the predicted poses")
         self._kp_jw = None
         if kp_joint_weight is not None and self.smplx_models:
             self._kp_jw = torch.as_tensor(np.asarray(kp_joint_weight, np.float32)).to(device).contiguous()
@@ -337,7 +343,45 @@ class GpuTrainer:
             return {"val_loss": lss, "pose_mse": lss}
         poses, lss = self.evaluate(batch["keypoints_3d"].to(self.device), batch["poses"].to(self.device))
         kp = self.keypoint_mse(poses, batch["target_keypoints_3d"], batch.get("betas"), batch.get("gender_id"))
-        return {"val_loss": lss + self.kp_weight * kp, "pose_mse": lss, "kp_mse": kp}
+        out = {"val_loss": lss + self.kp_weight * kp, "pose_mse": lss, "kp_mse": kp}
+        if self.val_metrics:
+            m = self.pose_metrics(poses, batch["target_keypoints_3d"], batch["poses"].to(self.device), batch.get("betas"),
+                                  batch.get("gender_id"))
+            for k in VAL_METRICS:   # a device scalar: the mean over the frames with W > 0 that have a value (NaN where none has)
+                has = (m["weight"] > 0) & torch.isfinite(m[k])
+                out[k] = torch.where(has, m[k], torch.zeros_like(m[k])).sum() / has.sum()
+        return out
+
+    def pose_metrics(self, poses, target_keypoints, target_poses=None, betas=None, gender_id=None) -> Dict[str, torch.Tensor]:
+        """SMPLX.pose_metrics of poses (N,T',66) against target_keypoints (N,T',17,3) and
+        target_poses (N,T',66) or None: one launch per body model on its rows, as
+        keypoint_mse walks them -> {"mpjpe", "pa_mpjpe", "mpjae", "weight"}, each (N T',)
+        and a view of one (N T', 4) device tensor. The keypoint weights are the trainer's
+        kp_joint_weight. validation_step averages each over the frames with W > 0 that have
+        a value: a frame with fewer than 3 positive weights has no pa_mpjpe and is left out
+        of that mean alone (a kp_joint_weight with fewer than 3 positive entries leaves
+        val/pa_mpjpe NaN)."""
+        if not self.smplx_models:
+            raise ValueError("pose_metrics needs smplx_models: the metrics run FK on the poses")
+        N, To = int(poses.shape[0]), int(poses.shape[1])
+        models = [self.smplx_models[g] for g in self._genders]
+        gid_host = None
+        if gender_id is not None:
+            gid_host = gender_id.detach().cpu().numpy() if isinstance(gender_id, torch.Tensor) else np.asarray(gender_id)
+        check_kp_args(self.kp_weight, len(models), poses.shape[2], N, To, models[0].num_betas, target_keypoints, betas, gid_host)
+        R = N * To
+        if target_poses is not None and tuple(target_poses.shape) != (N, To, KP_POSE_DIM):
+            raise ValueError(f"expected target poses {(N, To, KP_POSE_DIM)}, got {tuple(target_poses.shape)}")
+        P = poses.reshape(R, KP_POSE_DIM).contiguous()
+        K = target_keypoints.to(self.device, torch.float32).reshape(R, KP_JOINTS, 3).contiguous()
+        Tp = None if target_poses is None else target_poses.to(self.device, torch.float32).reshape(R, KP_POSE_DIM).contiguous()
+        b = None if betas is None else _rows_betas(betas.to(self.device, torch.float32), To)
+        out = torch.full((R, 4), float("nan"), device=self.device)
+        gid = None if gid_host is None else torch.as_tensor(gid_host.astype(np.int64)).to(self.device).repeat_interleave(To)
+        for i, m in enumerate(models):
+            rows = None if gid is None else torch.nonzero(gid == i).flatten().to(torch.int32).contiguous()
+            m.pose_metrics(P, K, betas=b, joint_weight=self._kp_jw, target_poses=Tp, rows=rows, out=out)
+        return {"mpjpe": out[:, 0], "pa_mpjpe": out[:, 1], "mpjae": out[:, 2], "weight": out[:, 3]}
 
     def keypoint_mse(self, poses, target_keypoints, betas=None, gender_id=None) -> torch.Tensor:
         """kp_mse of poses (N,T',66) against target_keypoints (N,T',17,3), the step's
@@ -366,7 +410,7 @@ class GpuTrainer:
 
     def validation_epoch_end(self, outputs):
         """pose_trainer.py:166-172: the mean of the batch means."""
-        losses = calc_mean_losses(outputs, ["pose_mse", "kp_mse", "val_loss"])
+        losses = calc_mean_losses(outputs, ["pose_mse", "kp_mse", "val_loss", *VAL_METRICS])
         return {"val_loss": losses["val_loss"], "log": {f"val/{k}": v for k, v in losses.items()}}
 
     def validate(self, val_ds, batch_size: int):
@@ -436,11 +480,12 @@ class GpuTrainer:
 
     @classmethod
     def from_checkpoint(cls, path, device="cuda", smplx_models=None, kp_weight: float = 0.0,
-                        kp_joint_weight=None) -> "GpuTrainer":
+                        kp_joint_weight=None, val_metrics: bool = False) -> "GpuTrainer":
         """A trainer that continues where `save_checkpoint` stopped. The keypoint term's
         arguments are the constructor's: the checkpoint does not store them."""
         tr = cls.__new__(cls)
-        tr._restore(path, device, smplx_models=smplx_models, kp_weight=kp_weight, kp_joint_weight=kp_joint_weight)
+        tr._restore(path, device, smplx_models=smplx_models, kp_weight=kp_weight, kp_joint_weight=kp_joint_weight,
+                    val_metrics=val_metrics)
         return tr
 
     # ------------------------------------------------------------------ fit
@@ -459,12 +504,15 @@ class GpuTrainer:
         `regressor` from the file: see `_restore`), counts the checkpoints of epochs
         <= e already in `ckpt_dir` toward `save_top_k`, and continues at e + 1;
         `max_epochs` counts from epoch 0.
-        Returns one {"epoch", "train/pose_mse", "val_loss", "ckpt"} per epoch run."""
+        Returns one {"epoch", "train/pose_mse", "val_loss", "ckpt"} per epoch run; with
+        val_metrics and a validation set also "val/mpjpe", "val/pa_mpjpe", "val/mpjae".
+        The checkpoints are ranked by val_loss either way."""
         start, kept = 0, []
         ckpt_dir = None if ckpt_dir is None else str(ckpt_dir)
         if resume_ckpt:
             ck = self._restore(resume_ckpt, self.device, smplx_models=self.smplx_models, kp_weight=self.kp_weight,
-                               kp_joint_weight=None if self._kp_jw is None else self._kp_jw.cpu().numpy())
+                               kp_joint_weight=None if self._kp_jw is None else self._kp_jw.cpu().numpy(),
+                               val_metrics=self.val_metrics)
             e = int(ck["epoch"])
             train_ds.on_epoch_end(e)
             start = e + 1
@@ -489,8 +537,11 @@ class GpuTrainer:
                 raise ValueError("fit: the training set is empty")
             train_loss = float(torch.stack(losses).mean())
             val_loss = train_loss
+            metrics = {}
             if val_ds is not None and len(val_ds):
-                val_loss = float(self.validate(val_ds, batch_size)["val_loss"])
+                val = self.validate(val_ds, batch_size)
+                val_loss = float(val["val_loss"])
+                metrics = {f"val/{k}": float(val["log"][f"val/{k}"]) for k in VAL_METRICS if f"val/{k}" in val["log"]}
             path = None
             if ckpt_dir and save_top_k != 0:
                 path = self.save_checkpoint(os.path.join(ckpt_dir, f"checkpoint_epoch={epoch}-val_loss={val_loss:.2f}.ckpt"),
@@ -505,7 +556,7 @@ class GpuTrainer:
                             path = None
                     kept = kept[:save_top_k]
             train_ds.on_epoch_end(epoch)
-            history.append({"epoch": epoch, "train/pose_mse": train_loss, "val_loss": val_loss, "ckpt": path})
+            history.append({"epoch": epoch, "train/pose_mse": train_loss, "val_loss": val_loss, "ckpt": path, **metrics})
         return history
 
 
@@ -561,6 +612,8 @@ def build_train_parser() -> argparse.ArgumentParser:
     p = build_parser()
     p.add_argument("--kp_weight", type=float, default=0.0,
                    help="weight of the keypoint term rel(FK(pred)) vs rel(keypoints) in the loss (0: pose MSE alone)")
+    p.add_argument("--val_metrics", action="store_true",
+                   help="validation also reports mpjpe, pa_mpjpe (metres) and mpjae (radians) of the predicted poses")
     return p
 
 
@@ -572,7 +625,8 @@ def run_train(argv=None) -> int:
     from .training_data import AmassDataset
     hp = build_train_parser().parse_args(argv)
     kp_weight = hp.kp_weight
-    del hp.kp_weight                    # not a hyper-parameter of the model: the checkpoint's hparams keep their keys
+    val_metrics = hp.val_metrics
+    del hp.kp_weight, hp.val_metrics    # not hyper-parameters of the model: the checkpoint's hparams keep their keys
     data_dir = Path(hp.data_dir)
     train_paths = _load_amass_path_list(data_dir / "train.csv")
     val_paths = _load_amass_path_list(data_dir / "valid.csv")
@@ -583,13 +637,14 @@ def run_train(argv=None) -> int:
     shape_path = Path(hp.amass) / "smplx_shapes.npz"
     if not shape_path.exists():
         raise FileNotFoundError(f"smplx_shapes.npz is not found under {hp.amass}")
-    kp_on = check_kp_args(kp_weight, 0 if kp_weight == 0 else 3) > 0.0
+    kp_on = check_kp_args(kp_weight, 0 if kp_weight == 0 else 3) > 0.0 or val_metrics   # either needs FK in the trainer
     smplx = load_smplx_models(None if hp.synthetic_smplx else Path(hp.amass) / "smplx", "cuda", batch_size=1024)
     train_ds = AmassDataset(smplx_models=smplx, amass_paths=train_paths, window_size=hp.win_size,
                             keypoint_format=hp.keypoint_format, shape_db_path=shape_path, target_keypoints=kp_on)
     val_ds = AmassDataset(smplx_models=smplx, amass_paths=val_paths, window_size=hp.win_size,
                           keypoint_format=hp.keypoint_format, target_keypoints=kp_on)
-    tr = GpuTrainer(IKPoseTrainer(hp), **({"smplx_models": smplx, "kp_weight": kp_weight} if kp_on else {}))
+    tr = GpuTrainer(IKPoseTrainer(hp), **({"smplx_models": smplx, "kp_weight": kp_weight, "val_metrics": val_metrics}
+                                          if kp_on else {}))
     if hp.resume_ckpt:
         print(f"resume from checkpoint: {hp.resume_ckpt}")
     else:
